@@ -2,20 +2,29 @@
 """bench.py — the contract bench (BASELINE.json metric: encode fps, 1080p preset medium, --me hex).
 
 `value` is REAL encode fps: the reference encoder's own objects with the binding's translation units (x265_amd/host/*.cpp) and libx265hip.so behind them —
-integration/_build/x265_hip_8bit — encoding a synthetic 1920x1080 clip with `--preset medium --me hex` (INTEGRATION.md says what the GPU serves).  One "step" = CHUNK = 12
+oracle/_ref/integration/x265_hip_8bit — encoding a synthetic 1920x1080 clip with `--preset medium --me hex` (INTEGRATION.md says what the GPU serves).  One "step" = CHUNK = 12
 frames of the clip; K steps are encoded in one run of ONE encoder, bracketed by barrier + synchronize, wall clock of this process (the encoder's own "encoded N
 frames in Xs" figure is reported beside it as `cli_fps`).  At N > 1 the job is the same and the encoder is still one: its device work is spread over the N GPUs
 (X265HIP_DEVICES; rank 0 runs it, the other ranks wait at the fences) — strong scaling; the chunk form (N encoders, one per GPU) and BASELINE
-configs[4]'s 8K shape are reported beside it, outside the timed region.  The same clip is then encoded by the unmodified reference encoder with the same
-arguments (oracle/_ref/x265_8bit built with the reference's own Release flags: `cpu_baseline`, kind "reference"; `cpu_baseline_vec`: with its intrinsics
-transforms), and the bitstreams must be byte-identical.  `roofline` is the kernel with the most device time in the timed encode, priced from the library's own
-HIP events around every launch (x265hip_device_time); `rooflines` holds the other named kernels and the stand-alone probes; `gpu_duty_cycle` = device time /
-wall clock.
+configs[4]'s 8K shape are reported beside it (--full), outside the timed region.  With --full the same clip is then encoded by the unmodified reference encoder
+with the same arguments (oracle/_ref/x265_8bit built with the reference's own Release flags: `cpu_baseline`, kind "reference"; `cpu_baseline_vec`: with its
+intrinsics transforms), and the bitstreams must be byte-identical.  `roofline` is the kernel with the most device time in the timed encode, priced from the
+library's own HIP events around every launch (x265hip_device_time); `rooflines` holds the other named kernels and (--full) the stand-alone probes;
+`gpu_duty_cycle` = device time / wall clock.
+
+Where the bound encoder was not built (it links the reference's objects: build() makes it only where the reference sources are), the line
+times the device-resident frame pass below instead — exactly --steps steps of F passes after --warmup steps — and `metric` says so; --dump-outputs
+then writes the reconstructed pictures of the last step as DIR/recon_chain<j>_{y,cb,cr}.npy (float32).
+
+A plain run (no --full) does only what the headline needs: the clip, the warm-up encode, the timed encode, the line.  --dump-outputs DIR writes what the timed
+encode returned for its last step: the bitstream bytes of its last CHUNK access units (decode order) as DIR/bitstream_last_step.npy and their sizes as
+DIR/access_unit_bytes_last_step.npy (float32 / float64; the clip is seeded, so the same arguments give the same inputs).
 
 Beside it (--frame-pass), `frame_pass` keeps the device-resident hot path of round 1 (quarter-pel planes, top-down motion search, prediction, residual
 chains, sa8d, borders on HBM-resident pictures, F frame chains per GPU, recon exchanged over RCCL when N > 1) with its own roofline.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs bench_outputs]
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full         # + CPU baselines, byte identity, stand-alone probes (and the chunk form / 8K shape at N > 1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (DESIGN.md §5 explains every field)."""
@@ -202,9 +211,11 @@ def valu_per_frame():
     return (total or None), os.path.relpath(files[-1], ROOT)
 
 
-def frame_pass_bench(args, rank, local_rank, world, steps, warmup):
+def frame_pass_bench(args, rank, local_rank, world, steps, warmup, headline=False):
     """The device-resident hot path (round 1's headline): F frame passes per GPU per step on HBM-resident pictures, recon exchanged over
-    RCCL when N > 1.  The timed loop is repeated until it has run for at least MIN_TIMED_S.  Returns the `frame_pass` object (rank 0) or None."""
+    RCCL when N > 1.  The timed loop is repeated until it has run for at least MIN_TIMED_S.  Returns the `frame_pass` object (rank 0) or None.
+    headline=True (the line's own workload where the bound encoder was not built): exactly `steps` timed steps, --dump-outputs writes the
+    reconstructed pictures of the last step, and the stage profiles and the CPU port run only with --full."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -264,8 +275,11 @@ def frame_pass_bench(args, rank, local_rank, world, steps, warmup):
     done = [[torch.cuda.Event(), torch.cuda.Event()] for _ in range(F)]
     got = [torch.cuda.Event(), torch.cuda.Event()]
 
+    last_rec = [None] * F
+
     def launch(j, k, ref):
         src, rec = pool[(k + j) % NPOOL], recons[j][k & 1]
+        last_rec[j] = rec
         st = streams[j]
         if st is None:                                          # F == 1: everything in order on the current stream
             run_pass(fps_[j].h, src, ref, preds[j], rec, stream)
@@ -314,18 +328,19 @@ def frame_pass_bench(args, rank, local_rank, world, steps, warmup):
     for _ in range(warmup):
         step()
     fence()
-    # the timed region lasts at least MIN_TIMED_S whatever --steps says: `steps` is raised (on every rank alike) from a first estimate
-    t0 = time.perf_counter()
-    for _ in range(10):
-        step()
-    fence()
-    est = (time.perf_counter() - t0) / 10
-    if world > 1:
-        t = torch.tensor([est], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        est = float(t.item())
-    steps = max(steps, int(MIN_TIMED_S / max(est, 1e-6)) + 1)
-    fence()
+    if not headline:
+        # the timed region lasts at least MIN_TIMED_S whatever --steps says: `steps` is raised (on every rank alike) from a first estimate
+        t0 = time.perf_counter()
+        for _ in range(10):
+            step()
+        fence()
+        est = (time.perf_counter() - t0) / 10
+        if world > 1:
+            t = torch.tensor([est], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            est = float(t.item())
+        steps = max(steps, int(MIN_TIMED_S / max(est, 1e-6)) + 1)
+        fence()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
@@ -338,6 +353,25 @@ def frame_pass_bench(args, rank, local_rank, world, steps, warmup):
         dt = float(t.item())
     ms_per_step = dt * 1e3 / steps
     fps = world * F * steps / dt
+    workload = ("1920x1080 8-bit 4:2:0, --me hex --merange 57 --subme 2, qp 28: frame pass = quarter-pel planes + top-down 2Nx2N "
+                "motion search (64/32/16/8) + luma/chroma prediction + dct/quant/dequant/idct/recon/sse chain (Y, Cb, Cr) + sa8d + borders; "
+                "F independent frame passes per GPU per step on F streams (x265 frame threads), each referencing the previous chain's recon; "
+                "the last chain's recon goes to the next rank (RCCL send/recv) when N > 1.  A builder-defined composition of reference "
+                "call sequences, not the encoder's own decisions (DESIGN.md §5)")
+    if headline:
+        if args.dump_outputs and rank == 0:
+            # the reconstructed pictures of the last timed step, one per chain, without their margins
+            arrays = {}
+            for j, rec in enumerate(last_rec):
+                a = rec.cpu().numpy()
+                arrays["recon_chain%d_y" % j] = a[:YB].reshape(R, S)[MARGIN:MARGIN + H, MARGIN:MARGIN + W]
+                arrays["recon_chain%d_cb" % j] = a[YB:YB + CB].reshape(RC, SC)[MC:MC + H // 2, MC:MC + W // 2]
+                arrays["recon_chain%d_cr" % j] = a[YB + CB:].reshape(RC, SC)[MC:MC + H // 2, MC:MC + W // 2]
+            save_outputs(args.dump_outputs, arrays)
+        if not args.full:
+            return None if rank != 0 else {"value": round(fps, 2), "unit": "frame passes/s", "steps": steps, "ms_per_step": round(ms_per_step, 4),
+                                           "timed_s": round(dt, 3), "workload": workload, "frames_per_step": world * F, "frames_in_flight_per_gpu": F,
+                                           "host_enqueue_ms_per_step": round(host_dt * 1e3 / steps, 4)}
 
     # ---- the dominant kernel's duration UNDER THE SAME LOAD as `fps` (F chains in flight): HIP events of chain 0's own stream
     hp.check(L.x265hip_framepass_set_profiling(fp.h, 1))
@@ -412,11 +446,7 @@ def frame_pass_bench(args, rank, local_rank, world, steps, warmup):
                 "frac": round(vpf * fps / peak, 4)}
     out = {
         "value": round(fps, 2), "unit": "frame passes/s", "steps": steps, "ms_per_step": round(ms_per_step, 4), "timed_s": round(dt, 3),
-        "workload": "1920x1080 8-bit 4:2:0, --me hex --merange 57 --subme 2, qp 28: frame pass = quarter-pel planes + top-down 2Nx2N "
-                    "motion search (64/32/16/8) + luma/chroma prediction + dct/quant/dequant/idct/recon/sse chain (Y, Cb, Cr) + sa8d + borders; "
-                    "F independent frame passes per GPU per step on F streams (x265 frame threads), each referencing the previous chain's recon; "
-                    "the last chain's recon goes to the next rank (RCCL send/recv) when N > 1.  A builder-defined composition of reference "
-                    "call sequences, not the encoder's own decisions (DESIGN.md §5)",
+        "workload": workload,
         "frames_per_step": world * F, "frames_in_flight_per_gpu": F, "pus_per_frame": 42900, "tus_per_frame": 8100,
         "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_src, "traffic_note": traffic_note,
@@ -537,28 +567,86 @@ def parse_served(lines):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+
+
+def access_units(stream):
+    """An HEVC Annex-B byte stream split into access units (H.265 7.4.2.4.4): a unit begins at the first VPS / SPS / PPS / AUD / prefix SEI / reserved
+    41..44, 48..55 NAL unit after a picture's last VCL NAL unit, or at a VCL NAL unit with first_slice_segment_in_pic_flag set.  Returns (start, end) byte ranges."""
+    starts, i = [], stream.find(b"\x00\x00\x01")
+    while i >= 0:
+        starts.append(i - 1 if i > 0 and stream[i - 1] == 0 else i)      # the zero_byte of a four-byte start code belongs to its NAL unit
+        i = stream.find(b"\x00\x00\x01", i + 3)
+    bounds, after_vcl = [], True
+    for k, p in enumerate(starts):
+        h = stream.index(b"\x00\x00\x01", p) + 3
+        t = (stream[h] >> 1) & 0x3F
+        vcl = t < 32
+        first = vcl and h + 2 < len(stream) and (stream[h + 2] & 0x80)
+        if after_vcl and (first or (not vcl and (t in (32, 33, 34, 35, 39) or 41 <= t <= 44 or 48 <= t <= 55))):
+            bounds.append(p)
+            after_vcl = False
+        if vcl:
+            after_vcl = True
+    return [(a, b) for a, b in zip(bounds, bounds[1:] + [len(stream)])]
+
+
+def save_outputs(out_dir, arrays):
+    """{name: array} as out_dir/<name>.npy in float32; above DUMP_MAX_BYTES in all, a fixed sample of each array (seed 0) with its positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if total > DUMP_MAX_BYTES:
+            k = int(a.size * DUMP_MAX_BYTES / total) // 3            # 4 bytes per value + 8 per position
+            pos = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+            np.save(os.path.join(out_dir, name + "_sample_positions.npy"), pos.astype(np.float64))
+            a = a[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
+def dump_outputs(out_dir, stream):
+    """--dump-outputs: what the timed encode returned for its last step = the bytes of its last CHUNK access units in decode order (an encoder's output of
+    CHUNK pictures; with --hash 1 each carries the MD5 of its reconstructed planes), as float32, and their sizes as float64.  Above DUMP_MAX_BYTES a fixed
+    sample of the bytes is written (seed 0) with its positions."""
+    import numpy as np
+    aus = access_units(stream)[-CHUNK:]
+    last = np.frombuffer(stream[aus[0][0]:], np.uint8) if aus else np.zeros(0, np.uint8)
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = np.array([b - a for a, b in aus], np.float64)
+    np.save(os.path.join(out_dir, "access_unit_bytes_last_step.npy"), sizes)
+    room = (DUMP_MAX_BYTES - sizes.nbytes) // 4
+    if last.size > room:
+        pos = np.sort(np.random.default_rng(0).choice(last.size, room // 3, replace=False))
+        np.save(os.path.join(out_dir, "bitstream_last_step_sample_positions.npy"), pos.astype(np.float64))
+        last = last[pos]
+    np.save(os.path.join(out_dir, "bitstream_last_step.npy"), last.astype(np.float32))
+
+
 def encode_bench(args, rank, local_rank, world, fence, allmax):
     """Real encode fps of ONE encoder on ONE clip: the K * CHUNK-frame segment of make_clip(seed 4321), 1920x1080, --preset medium --me hex.
-    N = 1: integration/_build/x265_hip_8bit on GPU 0.  N > 1: the SAME job, one encoder whose device work is spread over the N GPUs of the node (X265HIP_DEVICES=0..N-1:
+    N = 1: oracle/_ref/integration/x265_hip_8bit on GPU 0.  N > 1: the SAME job, one encoder whose device work is spread over the N GPUs of the node (X265HIP_DEVICES=0..N-1:
     reference-picture mirrors and source pictures take the GPUs in turn, SAD surfaces are built where the source picture lives from replicas of the reference
     pictures fed band by band device to device — x265's frame threads <-> GPUs, the reconstructed-reference exchange of BASELINE's north_star inside libx265hip.so),
     run by rank 0 while the other ranks hold their GPUs and wait at the fences: strong scaling, total work fixed.  Timed: wall clock between two fences around the
-    encoder run (after a W * CHUNK-frame warm-up run).  Afterwards, outside the timed region: the unmodified reference encoder on the same clip with the same
+    encoder run (after a W * CHUNK-frame warm-up run).  Afterwards, outside the timed region and only with --full: the unmodified reference encoder on the same clip with the same
     arguments (`cpu_baseline`; byte-identity of the two bitstreams), the reference with its intrinsics transforms (`cpu_baseline_vec`), and at N > 1 the chunk
     form (N encoders, one per GPU, each a closed-GOP repetition of the segment, the host cores split between them) and BASELINE configs[4]'s shape (7680x4320)."""
     import hashlib
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import encode_fps as ef
     ref, hip = os.path.join(ef.REF, "x265_8bit"), os.path.join(ef.INTEG, "x265_hip_8bit")
-    if not (os.path.exists(ref) and os.path.exists(hip)):
-        raise SystemExit("bench.py: oracle/_ref/x265_8bit and integration/_build/x265_hip_8bit are missing — build them where /root/reference exists "
-                         "(python -c 'import __graft_entry__ as g; g.build()'); they travel to the GPU box with the tree")
+    for exe in (ref, hip) if args.full else (hip,):
+        if not os.path.exists(exe):
+            raise SystemExit("bench.py: %s is missing — build() makes it where the reference sources are (oracle/Makefile, integration/Makefile), "
+                             "and oracle/_ref/ goes with the tree to where the bench runs" % os.path.relpath(exe, ROOT))
     from x265_amd.synth import make_clip
     frames, wframes = args.steps * CHUNK, max(args.warmup, 0) * CHUNK
     total = max(frames, wframes)
     clip = "/tmp/x265hip_bench_%d_r%d.yuv" % (os.getpid(), rank)
     if rank == 0 or world > 1:
-        make_clip(clip, W, H, total, seed=4321)              # (every rank keeps a copy: the chunk form beside the timed leg encodes a repetition per rank)
+        make_clip(clip, W, H, total, seed=4321, workers=8)   # (every rank keeps a copy: the chunk form beside the timed leg encodes a repetition per rank)
     cores = os.cpu_count() or 1
     quota = host_cpu_quota()
     usable = int(min(cores, quota)) if quota else cores      # CPUs the container's cgroup grants (16 of the 256 shown on the MI355X box)
@@ -595,11 +683,13 @@ def encode_bench(args, rank, local_rank, world, fence, allmax):
         if failed and world == 1:
             raise SystemExit("bench.py: x265_hip_8bit failed: " + r["tail"])
         res = {"dt": dt, "frames": frames, "cli_fps": r["fps"], "served": r["served"], "pools": pools, "threads_note": threads_note}
+        if args.dump_outputs and rank == 0 and not failed:
+            dump_outputs(args.dump_outputs, open(out_hip, "rb").read())
         if failed:
             # N > 1 and the one encoder over all GPUs did not finish (its cross-device path has never run between two physical GPUs on the pool this was built on):
             # the line falls back to the chunk form below as its timed leg, and says so
             res["one_encoder_error"] = (r.get("tail") or "x265_hip_8bit over all GPUs failed on rank 0")[-400:]
-        if not args.no_ref_encoder and rank == 0:
+        if args.full and not args.no_ref_encoder and rank == 0:
             t0 = time.perf_counter()
             r0 = ef._run(ref, base + threads + ["--frames", str(frames)], out_ref)
             dt_ref = time.perf_counter() - t0
@@ -624,9 +714,9 @@ def encode_bench(args, rank, local_rank, world, fence, allmax):
                     for q in (out_vec, out_vec + ".ni", out_ref + ".ni"):
                         if os.path.exists(q):
                             os.remove(q)
-        if world > 1:
+        if world > 1 and (args.full or failed):
             fence()
-            # ---- beside the timed leg, the chunk form: N encoders, one per GPU, each a closed-GOP repetition of the segment, the host's CPUs split between them
+            # ---- beside the timed leg, the chunk form (without --full only when the one encoder failed: then it is the headline): N encoders, one per GPU, each a closed-GOP repetition of the segment, the host's CPUs split between them
             per_rank = max(4, usable // world)
             envc = dict(os.environ, X265HIP_VERBOSE="1", X265HIP="require", HIP_VISIBLE_DEVICES=all_devs[0] if same_dev else all_devs[local_rank])
             out_chunk = clip + ".chunk.hevc"
@@ -658,7 +748,7 @@ def encode_bench(args, rank, local_rank, world, fence, allmax):
                                          "usable CPUs split); all frames of all encoders / wall clock" % (world, per_rank, usable)}
             # ---- ... and BASELINE configs[4]'s shape: 7680x4320 preset medium, one encoder over the N GPUs, with the reference beside it (a few frames: a reported
             # shape, not the metric)
-            if rank == 0 and not failed:
+            if args.full and rank == 0 and not failed:
                 clip8 = "/tmp/x265hip_bench8k_%d.yuv" % os.getpid()
                 out8, out8r = clip8 + ".gpu.hevc", clip8 + ".ref.hevc"
                 try:
@@ -782,6 +872,10 @@ def main():
     ap.add_argument("--probe-pairs", type=int, default=8, help="--lookahead-probe-only: (frame, reference) pairs per launch")
     ap.add_argument("--frames-in-flight", type=int, default=3,
                     help="frame pass: independent passes per GPU per step, each on its own HIP stream (x265 --frame-threads inside one device)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: the reference encoder on the same clip (cpu_baseline, cpu_baseline_vec, byte identity), the stand-alone "
+                         "kernel probes of `rooflines`, and at N > 1 the chunk form and BASELINE configs[4]'s 8K shape")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed encode returned for its last step as DIR/*.npy (see the module docstring)")
     args = ap.parse_args()
 
     import numpy as np
@@ -834,6 +928,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "integration", "x265_hip_8bit")):
+        # The bound encoder links the reference's own objects, so build() makes it only where the reference sources are.  Without it the line times
+        # what the tree alone runs: the frame pass of libx265hip.so's kernels (the `frame_pass` block of a --frame-pass run), and says so in `metric`.
+        fpb = frame_pass_bench(args, rank, local_rank, world, args.steps, args.warmup, headline=True)
+        if rank == 0:
+            print(json.dumps({"metric": "frame passes/s (1080p, the device-resident frame pass; the bound encoder is not built)", "value": fpb["value"],
+                              "unit": "frame passes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": fpb["ms_per_step"],
+                              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+                              "config": {"workload": fpb["workload"],
+                                         "why": "oracle/_ref/integration/x265_hip_8bit (the reference encoder's objects + x265_amd/host/*.cpp + libx265hip.so) is built "
+                                                "only where the reference sources are (integration/Makefile); `encode fps` needs it"},
+                              "frame_pass": fpb}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     enc = encode_bench(args, rank, local_rank, world, fence, allmax)
     dt = allmax(enc["dt"])
     fps = enc["frames"] / dt                                  # ONE encoder at every N: the same job, N GPUs (strong scaling)
@@ -878,26 +988,27 @@ def main():
                                 "note": "SURVEY 8d unique footprint of what a workgroup stages (one 64x64 source block + one 127x127 window per CTU) + the bytes it emits "
                                         "(16 x 16 windows and origins of 21 blocks): 33 621 B per complete CTU; rounds 1-3 charged 508 437 B (VERDICT r03)"}}
         probe_block, planes_probe = None, None
-        try:
-            pr = sadsurf_probe(np)
-            secs = pr["kernel_ns"] * 1e-9
-            ach = pr["ctus"] * pr["algorithmic_bytes_per_ctu"] / secs / 1e9
-            tad = pr["ctus"] * 16 * 4096 * 256 / secs / 1e12
-            probe_block = {"bound": "valu", "kernel": "sadsurf_ctu_kernel on whole 1080p pictures (tools/sadsurf_bench.py frame mode: %d launches of %d CTUs)" % (pr["launches"], pr["ctus_per_launch"]),
-                           "achieved": round(tad, 2), "peak": VALU_SAD_CEILING_T, "unit": "T absolute differences/s", "frac": round(tad / VALU_SAD_CEILING_T, 5),
-                           "traffic": ss_traffic, "traffic_source": ss_tfile, "traffic_note": ss_tnote, "launch_ms": round(pr["us_per_launch"] * 1e-3, 5),
-                           "hbm": {"achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 5),
-                                   "algorithmic_bytes_per_launch": int(pr["ctus_per_launch"] * pr["algorithmic_bytes_per_ctu"])}}
-            pp = pr.get("planes") or {}
-            if pp.get("spans") and pp.get("ns"):
-                psecs = pp["ns"] * 1e-9
-                planes_probe = {"bound": "hbm", "kernel": "subpel_planes8_kernel on whole padded 1080p pictures (%d launches inside the same probe): bytes = rows x padded width x (1 picture + 15 "
-                                                          "phase planes)" % pp["spans"],
-                                "achieved": round(pp["bytes"] / psecs / 1e9, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(pp["bytes"] / psecs / 1e9 / HBM_PEAK_GBPS, 5),
-                                "traffic": None, "algorithmic_bytes_per_launch": int(pp["bytes"] / pp["spans"]), "launch_ms": round(pp["ns"] / pp["spans"] * 1e-6, 5),
-                                "launch_ms_note": "HIP events around each launch (x265hip_device_time), after a warm-up repetition"}
-        except Exception as e:  # noqa: BLE001
-            probe_block = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+        if args.full:
+            try:
+                pr = sadsurf_probe(np)
+                secs = pr["kernel_ns"] * 1e-9
+                ach = pr["ctus"] * pr["algorithmic_bytes_per_ctu"] / secs / 1e9
+                tad = pr["ctus"] * 16 * 4096 * 256 / secs / 1e12
+                probe_block = {"bound": "valu", "kernel": "sadsurf_ctu_kernel on whole 1080p pictures (tools/sadsurf_bench.py frame mode: %d launches of %d CTUs)" % (pr["launches"], pr["ctus_per_launch"]),
+                               "achieved": round(tad, 2), "peak": VALU_SAD_CEILING_T, "unit": "T absolute differences/s", "frac": round(tad / VALU_SAD_CEILING_T, 5),
+                               "traffic": ss_traffic, "traffic_source": ss_tfile, "traffic_note": ss_tnote, "launch_ms": round(pr["us_per_launch"] * 1e-3, 5),
+                               "hbm": {"achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 5),
+                                       "algorithmic_bytes_per_launch": int(pr["ctus_per_launch"] * pr["algorithmic_bytes_per_ctu"])}}
+                pp = pr.get("planes") or {}
+                if pp.get("spans") and pp.get("ns"):
+                    psecs = pp["ns"] * 1e-9
+                    planes_probe = {"bound": "hbm", "kernel": "subpel_planes8_kernel on whole padded 1080p pictures (%d launches inside the same probe): bytes = rows x padded width x (1 picture + 15 "
+                                                              "phase planes)" % pp["spans"],
+                                    "achieved": round(pp["bytes"] / psecs / 1e9, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(pp["bytes"] / psecs / 1e9 / HBM_PEAK_GBPS, 5),
+                                    "traffic": None, "algorithmic_bytes_per_launch": int(pp["bytes"] / pp["spans"]), "launch_ms": round(pp["ns"] / pp["spans"] * 1e-6, 5),
+                                    "launch_ms_note": "HIP events around each launch (x265hip_device_time), after a warm-up repetition"}
+            except Exception as e:  # noqa: BLE001
+                probe_block = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         # ---- lookahead searches: live in the encode, and the probe at the encode's launch size ---------------------------------------------------------
         # ALGORITHMIC bytes per 8x8 lowres block of the P cost pass: SURVEY.md §8d per-call figures (sad / satd 2WHB, a quarter-pel candidate
         # adds the two half-pel blocks and the averaged one) over the calls the reference issues per block on this clip geometry, counted
@@ -919,20 +1030,22 @@ def main():
                        "traffic_note": (la_tnote + "; the profile's launches hold 35 pairs each: scaled to this run's pairs per launch") if la_traffic else la_tnote,
                        "algorithmic_bytes_per_launch": int(served["pairs_per_launch"] * LA_BLOCKS * LA_BYTES_PER_BLOCK),
                        "launch_ms": round(la["ms"] / served["search_launches"], 4), "launch_ms_note": "HIP events around each launch, summed over the timed encode"}
-        probe_pairs = int(min(64, max(1, round(served.get("pairs_per_launch", 8)))))
-        la_ms, la_blocks = lookahead_kernel_probe(L, hp, np, pairs=probe_pairs)
-        la_bytes = LA_BYTES_PER_BLOCK * la_blocks
-        ach = la_bytes / (la_ms * 1e-3) / 1e9
-        # what HBM has to deliver when caches work: the frame's plane + the reference's four half-pel planes once per pair, 22 B of results per block
-        uniq = (la_blocks // LA_BLOCKS) * 5 * 1024 * 608 + la_blocks * 22
-        la_probe = {"bound": "hbm", "kernel": "lookahead_p_kernel<u8> probe: %d identical (frame, reference) pairs per launch (the encode's average launch size), %d blocks x %.0f B"
-                                              % (la_blocks // LA_BLOCKS, la_blocks, LA_BYTES_PER_BLOCK),
-                    "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 5),
-                    "traffic": la_traffic if probe_pairs == 35 else None, "traffic_source": la_tfile, "traffic_note": la_tnote,
-                    "algorithmic_bytes_per_launch": int(la_bytes), "launch_ms": round(la_ms, 4),
-                    "launch_ms_note": "HIP events on the kernel's own stream, measured in this run",
-                    "unique_footprint": {"bytes_per_launch": uniq, "achieved": round(uniq / (la_ms * 1e-3) / 1e9, 2),
-                                         "frac": round(uniq / (la_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)}}
+        la_probe = None
+        if args.full:
+            probe_pairs = int(min(64, max(1, round(served.get("pairs_per_launch", 8)))))
+            la_ms, la_blocks = lookahead_kernel_probe(L, hp, np, pairs=probe_pairs)
+            la_bytes = LA_BYTES_PER_BLOCK * la_blocks
+            ach = la_bytes / (la_ms * 1e-3) / 1e9
+            # what HBM has to deliver when caches work: the frame's plane + the reference's four half-pel planes once per pair, 22 B of results per block
+            uniq = (la_blocks // LA_BLOCKS) * 5 * 1024 * 608 + la_blocks * 22
+            la_probe = {"bound": "hbm", "kernel": "lookahead_p_kernel<u8> probe: %d identical (frame, reference) pairs per launch (the encode's average launch size), %d blocks x %.0f B"
+                                                  % (la_blocks // LA_BLOCKS, la_blocks, LA_BYTES_PER_BLOCK),
+                        "achieved": round(ach, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 5),
+                        "traffic": la_traffic if probe_pairs == 35 else None, "traffic_source": la_tfile, "traffic_note": la_tnote,
+                        "algorithmic_bytes_per_launch": int(la_bytes), "launch_ms": round(la_ms, 4),
+                        "launch_ms_note": "HIP events on the kernel's own stream, measured in this run",
+                        "unique_footprint": {"bytes_per_launch": uniq, "achieved": round(uniq / (la_ms * 1e-3) / 1e9, 2),
+                                             "frac": round(uniq / (la_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)}}
         # ---- sub-pel plane bands: the one kernel of the encode that is bandwidth-shaped ------------------------------------------------------------------
         pl = clocks.get("sub-pel plane bands", {})
         pl_block = None
@@ -1040,7 +1153,7 @@ def main():
             "higher_is_better": True, "scaling": "weak" if (world == 1 or fallback) else "strong", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": "x265 --preset medium --me hex, 1920x1080 8-bit 4:2:0 (BASELINE configs[1]); ONE synthetic clip = the %d-frame segment of x265_amd/synth.make_clip "
                                    "(96x96 tiles with their own velocities + noise, seed 4321), encoded by ONE encoder (one step = %d frames): the reference encoder's objects + "
-                                   "x265_amd/host/*.cpp + libx265hip.so (integration/_build/x265_hip_8bit)%s: lookahead frame-cost "
+                                   "x265_amd/host/*.cpp + libx265hip.so (oracle/_ref/integration/x265_hip_8bit)%s: lookahead frame-cost "
                                    "estimates batched on the GPU, the residual quad-trees of CUs >= 32x32 (MFMA dct / quant / sign hiding / dequant / idct) as mailbox jobs to a resident GPU "
                                    "server, SAO statistics and the 35-mode intra scans of inter slices as jobs of the same server, integer-pel SADs and sub-pel SATDs of the motion search "
                                    "looked up in GPU-built SAD surfaces, luma sub-pel filter slots served from GPU-built fractional planes of each reference picture, psy-cost source halves "

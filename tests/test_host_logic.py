@@ -107,3 +107,49 @@ def test_committed_counter_profiles_were_collected_from_this_tree():
     assert files
     stamp = [l.split()[-1] for l in open(files[-1]) if l.startswith("# sources")]
     assert stamp and stamp[0] == bench.source_digest("cuserve.hip"), (files[-1], stamp)
+
+
+def test_make_clip_threads_write_the_same_bytes(tmp_path):
+    """make_clip(workers=N) (what bench.py uses) draws the noise in the same order on one thread and assembles frames on N: the bytes of the one-thread clip."""
+    from x265_amd.synth import make_clip
+    for kw in ({}, {"fade": True}, {"csp": "i422"}):
+        make_clip(str(tmp_path / "a.yuv"), 200, 136, 7, seed=11, **kw)
+        make_clip(str(tmp_path / "b.yuv"), 200, 136, 7, seed=11, workers=3, **kw)
+        assert (tmp_path / "a.yuv").read_bytes() == (tmp_path / "b.yuv").read_bytes(), kw
+
+
+def test_bench_dump_splits_access_units_and_keeps_the_last_step(tmp_path):
+    """bench.py --dump-outputs: the timed encode's bitstream split into access units (parameter sets and prefix SEI open one, a suffix SEI stays with its
+    picture, a picture's second slice does not open one); the last CHUNK units are written as float32 bytes and float64 sizes."""
+    import bench
+
+    def nal(t, first=True, body=b"\x11\x22"):
+        return b"\x00\x00\x00\x01" + bytes([t << 1, 1]) + bytes([0x80 if first else 0x00]) + body
+
+    head = nal(32) + nal(33) + nal(34) + nal(39)
+    pics = [nal(19 if k == 0 else 1) + nal(1, first=False) + nal(40) for k in range(bench.CHUNK + 2)]
+    stream = head + b"".join(pics)
+    aus = bench.access_units(stream)
+    assert len(aus) == bench.CHUNK + 2 and aus[0] == (0, len(head) + len(pics[0])) and aus[-1][1] == len(stream)
+    assert [b - a for a, b in aus[1:]] == [len(p) for p in pics[1:]]
+    bench.dump_outputs(str(tmp_path), stream)
+    data = np.load(tmp_path / "bitstream_last_step.npy")
+    sizes = np.load(tmp_path / "access_unit_bytes_last_step.npy")
+    assert data.dtype == np.float32 and sizes.dtype == np.float64
+    assert data.tobytes() == np.frombuffer(b"".join(pics[2:]), np.uint8).astype(np.float32).tobytes()
+    assert list(sizes) == [len(p) for p in pics[2:]]
+
+
+def test_bench_save_outputs_is_float32_and_samples_above_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs of the frame-pass line: arrays as float32 .npy; above DUMP_MAX_BYTES in all, the same seeded sample of each with its positions."""
+    import bench
+    a = np.arange(1000, dtype=np.uint8).reshape(10, 100)
+    bench.save_outputs(str(tmp_path / "all"), {"x": a})
+    assert np.array_equal(np.load(tmp_path / "all" / "x.npy"), a.reshape(-1).astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1200)
+    for d in ("s1", "s2"):
+        bench.save_outputs(str(tmp_path / d), {"x": a})
+    x, pos = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s1" / "x_sample_positions.npy")
+    assert x.size * 4 + pos.size * 8 <= 1200 and x.dtype == np.float32
+    assert np.array_equal(x, a.reshape(-1)[pos.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(x, np.load(tmp_path / "s2" / "x.npy"))

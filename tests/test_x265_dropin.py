@@ -20,9 +20,9 @@ REF = os.path.join(ROOT, "oracle", "_ref")
 
 
 def _need(name):
-    # the product's integration builds (reference objects + the binding + libx265hip.so) live in integration/_build, the reference alone and the
+    # the product's integration builds (reference objects + the binding + libx265hip.so) live in oracle/_ref/integration, the reference alone and the
     # emulated-ABI test binaries in oracle/_ref
-    p = os.path.join(ROOT, "integration", "_build", name) if "_hip" in name else os.path.join(REF, name)
+    p = os.path.join(REF, "integration", name) if "_hip" in name else os.path.join(REF, name)
     if not os.path.exists(p):
         pytest.skip("%s not built (needs /root/reference at build time: make -C integration hip)" % name)
     return p

@@ -4,7 +4,7 @@
 #
 #   tools/exp/gpu.sh <tag> <task> [task ...]
 #     tests [-k expr]      the GPU test tier (or a selection)
-#     bench                python bench.py (the contract line)
+#     bench                python bench.py --full (the contract line with everything beside it)
 #     configs23            BASELINE configs[2] / configs[3] at 4K: defaults (coefficient-mode CU jobs) vs X265HIP_CUSERVE_RDOQ=0 (RDOQ CUs stay on the host)
 #     ab <frames> <name:ENV=..,..> ...   interleaved A/B of the 1080p preset-medium bench encode
 #     rt                   tools/micro/cuserve_rt: the job round trip, with stage stamps
@@ -35,7 +35,7 @@ while [ $# -gt 0 ]; do
       sel=(); if [ "${1:-}" = "-k" ]; then sel=(-k "$2"); shift 2; fi
       timeout 1500 python -m pytest tests -m gpu -x -q "${sel[@]}" 2>&1 | tail -15 > $OUT/gputest.log; tail -3 $OUT/gputest.log ;;
     bench)
-      timeout 600 python bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-300 $OUT/bench.json ;;
+      timeout 600 python bench.py --full 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-300 $OUT/bench.json ;;
     configs23)
       # BASELINE configs[2] / configs[3] as JSON lines shaped like bench.py's (value, cpu_baseline with build flags, byte identity, served counts): CFG_ROUNDS
       # interleaved rounds (default 5), the bench line's thread arguments; then the coefficient-mode A/B (RDOQ CUs on the host vs as jobs)
@@ -56,7 +56,7 @@ while [ $# -gt 0 ]; do
     stats)
       clip /tmp/bench120.yuv 120
       HERE=$PWD
-      (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $HERE/$OUT/prof -o p -- $HERE/integration/_build/x265_hip_8bit --input /tmp/bench120.yuv --input-res 1920x1080 --fps 30 --frames 120 --preset medium --me hex -o /tmp/s.hevc > $HERE/$OUT/stats_run.log 2>&1)
+      (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $HERE/$OUT/prof -o p -- $HERE/oracle/_ref/integration/x265_hip_8bit --input /tmp/bench120.yuv --input-res 1920x1080 --fps 30 --frames 120 --preset medium --me hex -o /tmp/s.hevc > $HERE/$OUT/stats_run.log 2>&1)
       find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -r head -12 | cut -c1-180 ;;
     stress)
       n=$1; shift
@@ -68,14 +68,14 @@ while [ $# -gt 0 ]; do
         envs=(X265HIP=require)
         [ $((i % 2)) = 1 ] && envs+=(LD_PRELOAD=$R/allocshim.so ALLOCSHIM_SIZE=$((8 + 4 * elem)) ALLOCSHIM_ELEM=$elem ALLOCSHIM_OFFSET=$off ALLOCSHIM_WORD=2)
         [ $((i % 3)) = 0 ] && envs+=(X265HIP_REFPLANES=0)
-        env "${envs[@]}" TWO_ENCODERS_WATCHDOG=120 timeout 200 integration/_build/two_encoders_hip8 $D/g par > $D/run.log 2>&1 || { echo "run $i: exit $?"; tail -5 $D/run.log; bad=$((bad + 1)); continue; }
+        env "${envs[@]}" TWO_ENCODERS_WATCHDOG=120 timeout 200 oracle/_ref/integration/two_encoders_hip8 $D/g par > $D/run.log 2>&1 || { echo "run $i: exit $?"; tail -5 $D/run.log; bad=$((bad + 1)); continue; }
         for k in 0 1 2 3 4; do cmp -s $D/ref_$k.hevc $D/g_$k.hevc || { echo "run $i: session $k differs"; bad=$((bad + 1)); }; done
       done
       echo "concurrent encoders on the MI355X: $n runs (5 sessions each, two then three alive at a time), $bad mismatches or failures, $(( $(date +%s) - t0 )) s" | tee $OUT/concurrent_stress.txt ;;
     framestats)
       clip /tmp/bench120.yuv 120
       for b in hip ref; do
-        exe=integration/_build/x265_hip_8bit; [ $b = ref ] && exe=oracle/_ref/x265_8bit
+        exe=oracle/_ref/integration/x265_hip_8bit; [ $b = ref ] && exe=oracle/_ref/x265_8bit
         X265HIP=require $exe --input /tmp/bench120.yuv --input-res 1920x1080 --fps 30 --frames 120 --preset medium --me hex --csv $OUT/framestats_$b.csv --csv-log-level 2 -o /tmp/f.hevc 2>&1 | grep -E "^encoded" | tee $OUT/framestats_$b.log
       done
       python - $OUT <<'PY' | tee $OUT/frame_clocks.txt
@@ -101,7 +101,7 @@ PY
     callers)
       pat=$1; shift
       clip /tmp/bench240.yuv 240
-      X265HIP_CPUSAMPLE_STACK=1 X265HIP_CPUSAMPLE_OUT=/tmp/cs.bin LD_PRELOAD=tools/prof/libcpusample.so integration/_build/x265_hip_8bit --input /tmp/bench240.yuv --input-res 1920x1080 --fps 30 --frames 240 --preset medium --me hex --pools 24 -F 6 -o /tmp/p.hevc 2>&1 | grep -E "^encoded" > $OUT/callers_run.log
+      X265HIP_CPUSAMPLE_STACK=1 X265HIP_CPUSAMPLE_OUT=/tmp/cs.bin LD_PRELOAD=tools/prof/libcpusample.so oracle/_ref/integration/x265_hip_8bit --input /tmp/bench240.yuv --input-res 1920x1080 --fps 30 --frames 240 --preset medium --me hex --pools 24 -F 6 -o /tmp/p.hevc 2>&1 | grep -E "^encoded" > $OUT/callers_run.log
       python tools/prof/callers.py /tmp/cs.bin "$pat" 25 > $OUT/callers.txt 2>&1; head -60 $OUT/callers.txt | cut -c1-250 ;;
     pmc)
       HERE=$PWD
@@ -121,7 +121,7 @@ PY
       HERE=$PWD
       for c in fetch:FETCH_SIZE write:WRITE_SIZE; do
         (cd /tmp && export TMPDIR=/tmp && X265HIP=require X265HIP_CUSERVE=0 X265HIP_SAOSTATS=0 X265HIP_INTRASCAN=0 timeout 400 rocprofv3 --pmc ${c#*:} --kernel-trace --output-format csv -d $HERE/$OUT/pmc_encode/${c%%:*} -o p -- \
-           $HERE/integration/_build/x265_hip_8bit --input /tmp/bench30.yuv --input-res 1920x1080 --fps 30 --frames 30 --preset medium --me hex --pools 24 -F 6 -o /tmp/pe.hevc > $HERE/$OUT/pmc_encode_${c%%:*}.log 2>&1)
+           $HERE/oracle/_ref/integration/x265_hip_8bit --input /tmp/bench30.yuv --input-res 1920x1080 --fps 30 --frames 30 --preset medium --me hex --pools 24 -F 6 -o /tmp/pe.hevc > $HERE/$OUT/pmc_encode_${c%%:*}.log 2>&1)
       done
       find $OUT/pmc_encode -name "*kernel_trace.csv" -delete
       python tools/prof/pmc_kernels.py $OUT/pmc_encode "x265_hip_8bit, 30 frames 1080p preset medium --me hex, CU / SAO / intra jobs off" sadsurf.hip | tee $OUT/pmc_encode.txt | head -16 ;;
@@ -130,7 +130,7 @@ PY
       # the shell sees it, the encoder's own line — bound encoder and reference, three runs each
       clip /tmp/bench240.yuv 240
       for k in 1 2 3; do for b in hip ref; do
-        exe=integration/_build/x265_hip_8bit; [ $b = ref ] && exe=oracle/_ref/x265_8bit
+        exe=oracle/_ref/integration/x265_hip_8bit; [ $b = ref ] && exe=oracle/_ref/x265_8bit
         t0=$(date +%s%N)
         X265HIP=require X265HIP_DEBUG_STARTUP=1 $exe --input /tmp/bench240.yuv --input-res 1920x1080 --fps 30 --frames 240 --preset medium --me hex --pools 24 -F 6 -o /tmp/su.hevc > $OUT/startup_${b}_$k.log 2>&1
         t1=$(date +%s%N)
@@ -142,7 +142,7 @@ PY
     cpuprofile)
       clip /tmp/bench240.yuv 240
       for k in 1 2 3 4 5 6 7 8 9 10; do
-        X265HIP_CPUSAMPLE_OUT=/tmp/s$k.bin LD_PRELOAD=tools/prof/libcpusample.so integration/_build/x265_hip_8bit --input /tmp/bench240.yuv --input-res 1920x1080 --fps 30 --frames 240 --preset medium --me hex --pools 24 -F 6 -o /tmp/p.hevc 2>&1 | grep -E "encoded|x265hip" > $OUT/cpuprofile_run$k.log
+        X265HIP_CPUSAMPLE_OUT=/tmp/s$k.bin LD_PRELOAD=tools/prof/libcpusample.so oracle/_ref/integration/x265_hip_8bit --input /tmp/bench240.yuv --input-res 1920x1080 --fps 30 --frames 240 --preset medium --me hex --pools 24 -F 6 -o /tmp/p.hevc 2>&1 | grep -E "encoded|x265hip" > $OUT/cpuprofile_run$k.log
         python tools/prof/resolve.py /tmp/s$k.bin 200 > $OUT/cpu_profile_run$k.txt 2>&1
       done
       python tools/prof/merge.py $OUT/cpu_profile_run*.txt > $OUT/cpu_profile_bound_encoder.txt

@@ -16,7 +16,7 @@ run() { # name bits res frames args...
   a=(--input /tmp/vs_$name.yuv --input-res $res --fps 30 --frames $frames --hash 1 "$@")
   oracle/_ref/x265_${bits}bit "${a[@]}" -o /tmp/vs_ref.hevc > /dev/null 2>&1
   t0=$(date +%s)
-  X265HIP=require X265HIP_VERIFY=1 X265HIP_VERBOSE=1 integration/_build/x265_hip_${bits}bit "${a[@]}" -o /tmp/vs_hip.hevc > $OUT/$name.log 2>&1; rc=$?
+  X265HIP=require X265HIP_VERIFY=1 X265HIP_VERBOSE=1 oracle/_ref/integration/x265_hip_${bits}bit "${a[@]}" -o /tmp/vs_hip.hevc > $OUT/$name.log 2>&1; rc=$?
   same=no; cmp -s /tmp/vs_ref.hevc /tmp/vs_hip.hevc && same=yes
   echo "$name: $res $frames frames ${bits}-bit $*: exit $rc, bitstream identical to the reference's: $same, $(( $(date +%s) - t0 )) s under VERIFY; $(grep -c 'VERIFY FAILED' $OUT/$name.log) VERIFY failures; $(grep -E 'cuserve: [0-9]+ CU' $OUT/$name.log | cut -c1-120)" | tee -a $OUT/verify_soak.txt
 }
