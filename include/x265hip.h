@@ -946,13 +946,15 @@ int x265hip_cuserve_stats(x265hip_cuserve* cs, uint64_t* jobs, uint64_t* serverS
  * rectangles exactly as the reference does and hands them over; the device measures all classes of all planes in one job, luma first.
  *
  * The slot's pixel block, per plane p (0 .. planes-1) in turn: the reconstruction block, (h + 1) rows of (w + 1) samples starting at the sample ABOVE-LEFT
- * of the CTU's first one (row pitch w + 1), then the source block, h rows of w samples (row pitch w).  8-bit samples only (bitDepth 8).
+ * of the CTU's first one (row pitch w + 1), then the source block, h rows of w samples (row pitch w).  Samples are bytes at bitDepth 8 and uint16_t at
+ * bitDepth 10 and 12 (the band of a sample is sample >> (bitDepth - 5)).  A plane is up to 64 x 64: luma of a 64 CTU, and chroma of 4:2:0 (32 x 32),
+ * 4:2:2 (32 x 64) or 4:4:4 (64 x 64); header + pixel block must fit the slot (x265hip_cuserve_submit_sao: X265HIP_EINVAL otherwise).
  * Results: the slot's `levels` block read as int32: stats[plane][class][32] (3 * 5 * 32 entries) followed by count[plane][class][32]; class order
  * BO, EO_0, EO_1, EO_2, EO_3; an edge class fills entries 0..4 (the category order of SAO::s_eoTable: the values saoCuStatsE*_c add into their `stats`).
  * units[p].ready == the ticket when plane p's numbers are in place. */
 typedef struct x265hip_saojob
 {
-    uint32_t bitDepth;            /* 8 */
+    uint32_t bitDepth;            /* 8, 10 or 12 (x265hip_saojob_depths) */
     uint32_t planes;              /* 1 or 3 */
     uint32_t eo23;                /* 0: EO_2 and EO_3 are not measured (--limit-sao, sao.cpp:853-854): their entries are zero */
     uint32_t reserved;
@@ -963,14 +965,16 @@ typedef struct x265hip_saojob
     } plane[3];
 } x265hip_saojob;
 #define X265HIP_SAOJOB_STATS_ENTRIES (3 * 5 * 32)
-/* bytes of the pixel block the job describes */
+/* bytes of the pixel block the job describes (samples x 2 above 8 bit) */
 X265HIP_HD static inline int x265hipi_saojob_pixel_bytes(const x265hip_saojob* j)
 {
     int n = 0;
     for (uint32_t p = 0; p < j->planes && p < 3; p++)
         n += (j->plane[p].w + 1) * (j->plane[p].h + 1) + j->plane[p].w * j->plane[p].h;
-    return n;
+    return n * (j->bitDepth > 8 ? 2 : 1);
 }
+/* the bit depths this library's SAO statistics jobs accept: bit d set for depth d ((1 << 8) | (1 << 10) | (1 << 12) here).  Needs no device. */
+uint32_t x265hip_saojob_depths(void);
 /* hands the job to the device: `job` is copied into the mailbox in front of the pixel block the caller has written (x265hip_cuserve_slot's *pixels);
  * *seq = the ticket */
 int x265hip_cuserve_submit_sao(x265hip_cuserve* cs, int slot, const x265hip_saojob* job, uint32_t* seq);

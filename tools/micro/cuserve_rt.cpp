@@ -2,6 +2,7 @@
 // fills its slot, submits, and spins on the units' ready words, as x265_amd/host/x265_hip_cuserve.cpp does.  (measurement aid)
 //   cuserve_rt <mode 0|1> [iters] [stamps 0|1]   1, 4 and 16 submitting threads; 32x32 and 64x64 CUs (4:2:0, 8 bit, one transform size);
 //                                                stamps 1: the chain's stage stamps (job.reserved, x265hip_cujob_unit::reserved) of the first luma and the first Cb unit
+//   CUSERVE_RT_SAO_DEPTH=10|12: the SAO statistics jobs at that depth (16-bit samples), one luma plane per job as the seam sends them
 #include <atomic>
 #include <algorithm>
 #include <chrono>
@@ -122,6 +123,7 @@ int main(int argc, char** argv)
             fflush(stdout);
         }
     // ---- SAO statistics jobs (x265hip_saojob): a whole 64x64 CTU, three planes, every class; what SAO::calcSaoStatsCTU's seam hands over per CTU
+    const int saoDepth = getenv("CUSERVE_RT_SAO_DEPTH") ? atoi(getenv("CUSERVE_RT_SAO_DEPTH")) : 8, saoPlanes = saoDepth > 8 ? 1 : 3, last = saoPlanes - 1;
     for (int T : { 1, 4, 16 })
     {
         if ((only && only[0] != 's') || (onlyT && T != onlyT)) continue;
@@ -135,8 +137,8 @@ int main(int argc, char** argv)
             x265hip_cuserve_slot(cs, t, &job, &pixels, &units, &levels, &resi);
             x265hip_saojob sj;
             memset(&sj, 0, sizeof(sj));
-            sj.bitDepth = 8; sj.planes = 3; sj.eo23 = 1; sj.reserved = stamps;
-            for (int p = 0; p < 3; p++)
+            sj.bitDepth = saoDepth; sj.planes = saoPlanes; sj.eo23 = 1; sj.reserved = stamps;
+            for (int p = 0; p < saoPlanes; p++)
             {
                 const int n = p ? 32 : 64, po = p ? 2 : 0;
                 sj.plane[p].w = sj.plane[p].h = (uint16_t)n;
@@ -145,7 +147,10 @@ int main(int argc, char** argv)
             const int bytes = x265hipi_saojob_pixel_bytes(&sj);
             std::vector<unsigned char> src(bytes);
             uint32_t s = 99 + t;
-            for (auto& b : src) { s = s * 1664525u + 1013904223u; b = (unsigned char)(120 + ((s >> 24) & 31)); }
+            if (saoDepth > 8)
+                for (size_t k = 0; k < src.size(); k += 2) { s = s * 1664525u + 1013904223u; const uint16_t v = (uint16_t)((120 + ((s >> 24) & 31)) << (saoDepth - 8) | (s >> 8 & 3)); memcpy(&src[k], &v, 2); }
+            else
+                for (auto& b : src) { s = s * 1664525u + 1013904223u; b = (unsigned char)(120 + ((s >> 24) & 31)); }
             while (!go.load()) {}
             for (int i = 0; i < iters + 100 && !failed; i++)
             {
@@ -155,7 +160,7 @@ int main(int argc, char** argv)
                 uint32_t seq = 0;
                 if (x265hip_cuserve_submit_sao(cs, t, &sj, &seq)) { fprintf(stderr, "submit_sao: %s\n", x265hip_last_error()); failed = true; break; }
                 double tl = 0;
-                for (int p = 0; p < 3 && !failed; p++)
+                for (int p = 0; p < saoPlanes && !failed; p++)
                 {
                     uint64_t spins = 0;
                     while (__atomic_load_n(&units[p].ready, __ATOMIC_ACQUIRE) != seq)
@@ -163,11 +168,11 @@ int main(int argc, char** argv)
                     if (p == 0) tl = now_us() - t0;
                 }
                 const double tw = now_us() - t0;
-                if (i >= 100) { luma[t].push_back(tl); whole[t].push_back(tw); dev0[t].push_back(units[0].fwdTicks * 0.01); dev2[t].push_back(units[2].fwdTicks * 0.01); }
+                if (i >= 100) { luma[t].push_back(tl); whole[t].push_back(tw); dev0[t].push_back(units[0].fwdTicks * 0.01); dev2[t].push_back(units[last].fwdTicks * 0.01); }
                 if (i >= 100 && stamps && t == 0)
-                    for (int p = 0; p < 3; p += 2)
+                    for (int w = 0; w < 2; w++)
                         for (int k = 0; k < 5; k++)
-                            sst[p / 2][k].push_back(((units[p].reserved[k >> 1] >> (16 * (k & 1))) & 0xffff) * 0.01);
+                            sst[w][k].push_back(((units[w ? last : 0].reserved[k >> 1] >> (16 * (k & 1))) & 0xffff) * 0.01);
             }
         };
         std::vector<std::thread> th;
@@ -177,15 +182,16 @@ int main(int argc, char** argv)
         for (auto& x : th) x.join();
         const double wall = now_us() - w0;
         auto med = [](std::vector<std::vector<double>>& v) { std::vector<double> a; for (auto& x : v) a.insert(a.end(), x.begin(), x.end()); std::sort(a.begin(), a.end()); return a.empty() ? 0.0 : a[a.size() / 2]; };
-        printf("%s, SAO statistics of a 64x64 CTU (4:2:0, 8 bit, 5 classes x 3 planes), %2d thread%s: luma ready median %6.1f us (%4.1f us of it on the device), all planes %6.1f us (%4.1f on the device); "
-               "%.0f jobs/s in total\n", mode ? "one launch per job" : "resident server   ", T, T > 1 ? "s" : " ", med(luma), med(dev0), med(whole), med(dev2), (double)T * (iters + 100) / (wall * 1e-6));
+        printf("%s, SAO statistics of a 64x64 CTU (4:2:0, %d bit, 5 classes x %d plane%s), %2d thread%s: luma ready median %6.1f us (%4.1f us of it on the device), all planes %6.1f us (%4.1f on the device); "
+               "%.0f jobs/s in total\n", mode ? "one launch per job" : "resident server   ", saoDepth, saoPlanes, saoPlanes > 1 ? "s" : "", T, T > 1 ? "s" : " ", med(luma), med(dev0), med(whole), med(dev2),
+               (double)T * (iters + 100) / (wall * 1e-6));
         if (stamps)
             for (int w = 0; w < 2; w++)
             {
                 double m[5];
                 for (int k = 0; k < 5; k++) { std::sort(sst[w][k].begin(), sst[w][k].end()); m[k] = sst[w][k].empty() ? 0 : sst[w][k][sst[w][k].size() / 2]; }
                 printf("      %s plane, us since the doorbell was seen (medians): plane starts %.2f, histograms cleared %.2f, samples classified %.2f, edge classes totalled %.2f, published %.2f\n",
-                       w ? "Cr  " : "luma", m[0], m[1], m[2], m[3], m[4]);
+                       w ? (saoPlanes > 1 ? "Cr  " : "luma (again)") : "luma", m[0], m[1], m[2], m[3], m[4]);
             }
         fflush(stdout);
     }

@@ -1329,24 +1329,45 @@ __device__ __forceinline__ int wave_total_lane63(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
     return v;
 }
+// A column word holds a count and a sum of differences: 8-bit samples (|d| <= 255) count in the high and sum in the low half-word; 16-bit samples (|d| <= 4 095
+// at 12 bit: a column's sum reaches 64 x 4 095 = 262 080) count from bit 24 up over a 24-bit signed sum (64 << 24 = 2^30 still leaves the sign bit alone)
+template <typename P> struct SaoColumn;
+template <> struct SaoColumn<uint8_t>
+{
+    static constexpr int kCount = 1 << 16;
+    __device__ static int sum(int v) { return (int)(short)(v & 0xffff); }
+    __device__ static int band(int c, int) { return c >> 3; }
+};
+template <> struct SaoColumn<uint16_t>
+{
+    static constexpr int kCount = 1 << 24;
+    __device__ static int sum(int v) { return (int)((uint32_t)v << 8) >> 8; }
+    // c >> (bitDepth - 5); the mask keeps a sample above the job's depth inside the 32 band columns
+    __device__ static int band(int c, int shift) { return (c >> shift) & 31; }
+};
+
+template <typename P>
 __device__ __forceinline__ void run_sao(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0)
 {
+    using Col = SaoColumn<P>;
+    constexpr int kCntShift = sizeof(P) == 1 ? 16 : 24;
     const x265hip_saojob& j = *reinterpret_cast<const x265hip_saojob*>(&L.job);
     // LDS (over tile[]): [0..159] sums of class c bin b at c * 32 + b, [160..319] counts — what goes out; [320..1599] the edge classes, [1600..3647] the band
-    // class: a COLUMN per lane for every bin (edge class c, sign sum e in 0..4: 320 + ((c * 5 + e) * 64 + lane); band b: 1600 + b * 64 + lane), count in the high
-    // and sum in the low half of a word.  A sample is ONE ds_add per class into its lane's column of the bin it falls in (a zero when it lies outside the class's
+    // class: a COLUMN per lane for every bin (edge class c, sign sum e in 0..4: 320 + ((c * 5 + e) * 64 + lane); band b: 1600 + b * 64 + lane), a count and a
+    // sum packed in one word (SaoColumn).  A sample is ONE ds_add per class into its lane's column of the bin it falls in (a zero when it lies outside the class's
     // rectangle): lanes never meet on an address, the four waves share the columns (the add is atomic), and nothing is selected or compared per bin
-    // (a column sees at most 64 samples: the count fits the high half-word, the sum of differences, |d| <= 255, the low one)
+    // (a column sees at most 64 samples)
     int* hist = reinterpret_cast<int*>(&L.tile[0]);
     int32_t* out = reinterpret_cast<int32_t*>(s->levels);
     const int tid = threadIdx.x, lx = tid & 63, ly = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned char* at = L.pix;
+    const int bandShift = (int)j.bitDepth - 5;
+    const P* at = reinterpret_cast<const P*>(L.pix);
     const int planes = j.planes < 3 ? (int)j.planes : 3;
     for (int p = 0; p < planes; p++)
     {
         const int w = j.plane[p].w, h = j.plane[p].h, stride = w + 1;
-        const unsigned char* rec0 = at + stride + 1;
-        const unsigned char* fenc0 = at + (w + 1) * (h + 1);
+        const P* rec0 = at + stride + 1;
+        const P* fenc0 = at + (w + 1) * (h + 1);
         at = fenc0 + w * h;
         uint32_t stamp[5] = { 0, 0, 0, 0, 0 };                         // job.reserved != 0 (tools/micro/cuserve_rt): 100 MHz ticks since the doorbell at five points
 #define XH_SSTAMP(i) do { if (j.reserved) stamp[i] = (uint32_t)(wall_clock64() - t0) & 0xffffu; } while (0)
@@ -1372,16 +1393,16 @@ __device__ __forceinline__ void run_sao(SlotOut* s, JobLds& L, uint32_t seq, uin
         // else hides the LDS latency.  The second row of the last trip may lie below the plane: it is read from the first one's place and adds zeros
         auto classify = [&](int y, bool valid) __attribute__((always_inline))
         {
-            const unsigned char* r = rec0 + y * stride + xi;
+            const P* r = rec0 + y * stride + xi;
             const int c = r[0], d = (int)fenc0[y * w + xi] - c;
-            const int one = valid ? (1 << 16) + d : 0;
+            const int one = valid ? Col::kCount + d : 0;
             // sign(c - neighbour) = the difference clamped to [-1, 1] (v_med3_i32)
             const int sR = clip3i(-1, 1, c - (int)r[1]), sL = clip3i(-1, 1, c - (int)r[-1]), sD = clip3i(-1, 1, c - (int)r[stride]), sU = clip3i(-1, 1, c - (int)r[-stride]);
             const int sDR = clip3i(-1, 1, c - (int)r[stride + 1]), sUL = clip3i(-1, 1, c - (int)r[-stride - 1]);
             const int sDL = clip3i(-1, 1, c - (int)r[stride - 1]), sUR = clip3i(-1, 1, c - (int)r[-stride + 1]);
             // (the row tests are wave-uniform: y is)
             const bool r0 = y < y1[0], r1 = y < y1[1], r2 = y >= y0[2] && y < y1[2], r3 = y >= y0[3] && y < y1[3], r4 = y >= y0[4] && y < y1[4];
-            __hip_atomic_fetch_add(bandCol + (c >> 3) * 64, cx0 && r0 ? one : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(bandCol + Col::band(c, bandShift) * 64, cx0 && r0 ? one : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_add(edgeCol + (0 * 5 + sR + sL + 2) * 64, cx1 && r1 ? one : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_add(edgeCol + (1 * 5 + sD + sU + 2) * 64, cx2 && r2 ? one : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_add(edgeCol + (2 * 5 + sDR + sUL + 2) * 64, cx3 && r3 ? one : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1402,7 +1423,7 @@ __device__ __forceinline__ void run_sao(SlotOut* s, JobLds& L, uint32_t seq, uin
             for (int e = 0; e < 5; e++)
             {
                 const int v = hist[320 + (ly * 5 + e) * 64 + lx];
-                const int sumL = (int)(short)(v & 0xffff), cntL = (v - sumL) >> 16;
+                const int sumL = Col::sum(v), cntL = (v - sumL) >> kCntShift;
                 const int ts = wave_total_lane63(sumL), tc = wave_total_lane63(cntL);
                 const int k = e == 0 ? 1 : e == 1 ? 2 : e == 2 ? 0 : e;
                 if (lx == 63)
@@ -1422,8 +1443,8 @@ __device__ __forceinline__ void run_sao(SlotOut* s, JobLds& L, uint32_t seq, uin
             for (int i = 0; i < 8; i++)
             {
                 const int v = col[i];
-                const int sL = (int)(short)(v & 0xffff);
-                sumB += sL; cntB += (v - sL) >> 16;
+                const int sL = Col::sum(v);
+                sumB += sL; cntB += (v - sL) >> kCntShift;
             }
             // eight consecutive lanes: xor 1, 2 (quad DPP), then lane + 4 of the same row
             sumB += __builtin_amdgcn_update_dpp(0, sumB, 0xB1, 0xf, 0xf, false); cntB += __builtin_amdgcn_update_dpp(0, cntB, 0xB1, 0xf, 0xf, false);
@@ -1625,7 +1646,7 @@ __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L
     if (!cuJob)
     {
         const x265hip_intrajob& ij = *reinterpret_cast<const x265hip_intrajob*>(&L.job);
-        if (!(ij.mark & X265HIP_INTRAJOB_MARK)) run_sao(s, L, ticket, t0);
+        if (!(ij.mark & X265HIP_INTRAJOB_MARK)) { if (ij.bitDepth > 8) run_sao<uint16_t>(s, L, ticket, t0); else run_sao<uint8_t>(s, L, ticket, t0); }
         else if (ij.bitDepth > 8) run_intra<uint16_t>(s, L, ticket, t0);
         else run_intra<uint8_t>(s, L, ticket, t0);
     }
@@ -2069,10 +2090,15 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
     return X265HIP_OK;
 }
 
+uint32_t x265hip_saojob_depths(void)
+{
+    return (1u << 8) | (1u << 10) | (1u << 12);
+}
+
 int x265hip_cuserve_submit_sao(x265hip_cuserve* cs, int slot, const x265hip_saojob* job, uint32_t* seqOut)
 {
     if (!cs || slot < 0 || slot >= cs->slots || !job || !seqOut) return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit_sao: slot %d", slot);
-    bool ok = job->bitDepth == 8 && job->planes >= 1 && job->planes <= 3;
+    bool ok = job->bitDepth < 32 && ((x265hip_saojob_depths() >> job->bitDepth) & 1) && job->planes >= 1 && job->planes <= 3;
     for (uint32_t p = 0; ok && p < job->planes; p++)
     {
         ok = job->plane[p].w >= 1 && job->plane[p].w <= 64 && job->plane[p].h >= 1 && job->plane[p].h <= 64;
@@ -2080,7 +2106,8 @@ int x265hip_cuserve_submit_sao(x265hip_cuserve* cs, int slot, const x265hip_saoj
             ok = job->plane[p].x1[c] <= job->plane[p].w && job->plane[p].y1[c] <= job->plane[p].h;
     }
     const int bytes = ok ? x265hipi_saojob_pixel_bytes(job) : 0;
-    if (!ok || bytes > X265HIP_CUJOB_PIXEL_BYTES)
+    // (the device fetches header + pixels in whole 512-byte steps, ticket_bytes: the last step has to end inside the slot's pixel block)
+    if (!ok || (128 + bytes + 511) / 512 * 512 > 128 + X265HIP_CUJOB_PIXEL_BYTES)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit_sao: depth %u, %u planes, luma %ux%u", job->bitDepth, job->planes, job->plane[0].w, job->plane[0].h);
     SlotIn* s = cs->in + slot;
     uint32_t run = cs->seq[slot].load(std::memory_order_relaxed) + 1;

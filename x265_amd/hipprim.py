@@ -191,6 +191,7 @@ PROTOTYPES = {
     "x265hip_cuserve_submit": (i32, [vp, i32, C.POINTER(u32)]),
     "x265hip_cuserve_poke": (i32, [vp, i32]),
     "x265hip_cuserve_submit_sao": (i32, [vp, i32, vp, vp]),
+    "x265hip_saojob_depths": (u32, []),
     "x265hip_cuserve_submit_intra": (i32, [vp, i32, vp, vp]),
     "x265hip_cuserve_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     "x265hip_device_time": (i32, [i32, vp, vp, vp]),

@@ -1,6 +1,10 @@
 // x265_hip_saostats.cpp — SAO statistics as jobs of the CU-job service (split from x265_hip_cuserve.cpp in round 6).
 #include "x265_hip_cuserve.h"
 
+// weak: the CPU emulation of the job ABI (tests/support) that the same seam objects are also linked against does not define it; there it is NULL and the seam
+// stays at 8 bit, whose jobs every implementation of the ABI accepts
+extern "C" uint32_t x265hip_saojob_depths(void) __attribute__((weak));
+
 namespace X265_NS {
 
 using namespace cusvc;
@@ -11,10 +15,12 @@ using namespace cusvc;
 // encoder's CPU time in round 4's profile).  Its result is a function of the deblocked CTU (with the row above and the column to the left), the source CTU and
 // the rectangles the reference measures: the seam below computes the rectangles exactly as the reference does, hands the two blocks to the device — one job
 // for all planes when luma is asked for (the chroma planes are measured while this thread runs the luma offsets' RDO) — and adds the sums and counts it gets
-// back where the reference's primitives add theirs.  8-bit builds; X265HIP_SAOSTATS=0 switches it off; X265HIP_VERIFY recomputes with the reference's body.
+// back where the reference's primitives add theirs.  Every chroma format; 8-bit builds, and 10 / 12-bit builds when the linked library's SAO jobs take that
+// depth (x265hip_saojob_depths); X265HIP_SAOSTATS=0 switches it off, =1 on at every such depth; X265HIP_VERIFY recomputes with the reference's body.
 namespace {
 
 std::atomic<int> g_saoState(0);  // 0 undecided, 1 on, -1 off (written by whichever thread decides or sees the device fail)
+constexpr bool kSaoHighDepthDefault = true;   // 10 / 12-bit builds without X265HIP_SAOSTATS: served (not slower at Main10)
 bool g_saoParts = false;         // X265HIP_SAOSTATS_PARTS=4: the luma plane goes as two jobs (upper / lower half).  Measured: 3 jobs per CTU 33.2 fps, 4 jobs 32.6, SAO on the host 30.9
 struct alignas(64) SaoCounters { std::atomic<uint64_t> jobs, planes, hostPlanes, waits, waitCycles, ahead; };
 SaoCounters g_saoCount[16];
@@ -57,7 +63,10 @@ bool sao_enabled()
             const char* table = getenv("X265HIP_TABLE");
             if (getenv("X265HIP_SAOSTATS_PARTS")) g_saoParts = atoi(getenv("X265HIP_SAOSTATS_PARTS")) > 3;
             if (getenv("X265HIP_SAOSTATS_AHEAD")) g_saoAhead = atoi(getenv("X265HIP_SAOSTATS_AHEAD")) != 0;
-            if (X265_DEPTH != 8 || (env && !strcmp(env, "0")) || (all && !strcmp(all, "0")) || (table && !strcmp(table, "percall")))
+            // above 8 bit: only where the linked library takes jobs of this depth; on unless switched off (the Main10 / Main12 A/B)
+            const bool depthServed = X265_DEPTH == 8 || (x265hip_saojob_depths && ((x265hip_saojob_depths() >> X265_DEPTH) & 1));
+            const bool wanted = X265_DEPTH == 8 || kSaoHighDepthDefault || (env && !strcmp(env, "1"));
+            if (!depthServed || !wanted || (env && !strcmp(env, "0")) || (all && !strcmp(all, "0")) || (table && !strcmp(table, "percall")))
                 g_saoState = -1;
             else
             {
@@ -305,7 +314,7 @@ void SAO::calcSaoStatsCTU(int addr, int plane)
     const bool chroma = m_param->internalCsp != X265_CSP_I400 && m_frame->m_fencPic->m_picCsp != X265_CSP_I400;
     const SAOParam* sp = m_frame->m_encData->m_saoParam;
     // luma asked for: the chroma planes ride along when the reference is going to ask for them whatever the luma decision (no --limit-sao, :1299-1306)
-    const int planesWithLuma = chroma && !m_param->bLimitSAO && sp && sp->bSaoFlag[1] && m_param->internalCsp == X265_CSP_I420 ? 3 : 1;
+    const int planesWithLuma = chroma && !m_param->bLimitSAO && sp && sp->bSaoFlag[1] ? 3 : 1;
     if (!cur)
     {
         for (SaoJob& t : t_saoSet)
@@ -314,7 +323,7 @@ void SAO::calcSaoStatsCTU(int addr, int plane)
         {
             if (plane == 0)
                 sao_submit(*cur, this, addr, 0, planesWithLuma);
-            else if (plane == 1 && m_param->internalCsp == X265_CSP_I420)
+            else if (plane == 1)
                 sao_submit(*cur, this, addr, 1, 2);
             if (!cur->active) cur = NULL;
         }
