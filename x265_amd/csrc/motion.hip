@@ -1,10 +1,8 @@
 // motion.hip — MotionEstimate::motionEstimate for a whole batch of PUs in one launch (gfx950).
 //
-// Reference semantics (bit-exact MV and cost): source/encoder/motion.cpp — motionEstimate :739-1569 (predictor,
-// zero and candidate tests :761-812; DIA :831-852; HEX :855-944; FULL :1397-1441; bestpre/bmv merge :1449-1455;
-// sub-pel refine :1504-1561 driven by workload[] :48-58), subpelCompare :1571 (luma_hpp / luma_vpp / luma_hvpp +
-// sad / satd), COPY*_IF_LT tie-breaking (common.h:183-204), MV::clipped / checkRange (mv.h:88-100),
-// BitCost::mvcost (bitcost.h:42-45: u16 sum of two table entries).
+// Reference semantics (bit-exact MV and cost): source/encoder/motion.cpp — motionEstimate :739-1569, whose control flow is
+// mesearch.h's (this file holds the evaluator MeCtx, the SEA search and the launches), subpelCompare :1571 (luma_hpp / luma_vpp /
+// luma_hvpp + sad / satd), BitCost::mvcost (bitcost.h:42-45: u16 sum of two table entries).
 //
 // Mapping: ONE WAVE PER PU, 4 independent waves per workgroup.  The search is a serial chain of decisions, but every
 // decision variable (bmv, bcost, dir ...) is wave-uniform, so the wave runs the reference's control flow in lockstep
@@ -20,32 +18,10 @@
 #include "common.h"
 #include "tiles.h"
 #include "filters.h"
-#include "searchrange.h"
-#include "mestar.h"
-#include "meumh.h"
+#include "mesearch.h"
 #include <cstdlib>
 
 namespace xh {
-
-struct Mv { int x, y; };
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-template <typename P> struct Packed;
-template <> struct Packed<uint8_t>
-{
-    typedef uint32_t T;
-    static __device__ __forceinline__ unsigned sad(T a, T b, unsigned acc) { return __builtin_amdgcn_sad_u8(a, b, acc); }
-};
-template <> struct Packed<uint16_t>
-{
-    typedef uint2 T;
-    static __device__ __forceinline__ unsigned sad(T a, T b, unsigned acc)
-    {
-        acc = __builtin_amdgcn_sad_u16(a.x, b.x, acc);
-        return __builtin_amdgcn_sad_u16(a.y, b.y, acc);
-    }
-};
 
 template <typename P>
 struct MeCtx
@@ -67,6 +43,8 @@ struct MeCtx
     int64_t strideC;
     P* fencCb;                           // LDS, (w/2) x (h/2) each
     P* fencCr;
+    SeaPlanes sea;                       // --me sea: window-sum planes of the reference
+    int bx, by;                          // PU origin in the picture
 
     __device__ __forceinline__ int mvcost(int qx, int qy) const
     {
@@ -299,23 +277,163 @@ struct MeCtx
             v += chroma_term(q);
         return v;
     }
+
+    // ---- mesearch.h contract
+    static constexpr int kSubpelGroup = 1;
+    static constexpr int kFullGroup = 4;
+    static constexpr bool kSea = true;
+    __device__ __forceinline__ void opening(Mv pmv, Mv fp, bool fpOk, bool zeroOk, int (&out)[3]) const
+    {
+        out[0] = subpel(pmv, 0);
+        if (fpOk) out[1] = fullpel_cost(fp.x, fp.y, 2);
+        if (zeroOk) out[2] = fullpel_cost(0, 0, 2);
+    }
+    // sad_x3 / sad_x4 steps: K = 3, 6 as groups of three, K = 4, 8 as groups of four, each group side by side on lane groups
+    template <int K>
+    __device__ __forceinline__ void pattern(const Mv (&m)[K], int (&out)[K], int n = K) const
+    {
+        constexpr int S = K % 3 ? 4 : 3;
+#pragma unroll
+        for (int k0 = 0; k0 < K; k0 += S)
+        {
+            Mv cand[4];
+            int costs[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) cand[k] = m[k0 + (k < S ? k : S - 1)];
+            const int cnt = min(S, n - k0);
+            sad_multi(cnt, cand, costs);
+#pragma unroll
+            for (int k = 0; k < S; k++)
+                if (k < cnt) out[k0 + k] = costs[k] + mvcost(m[k0 + k].x * 4, m[k0 + k].y * 4);
+        }
+    }
+    template <int K>
+    __device__ __forceinline__ void subpels(const Mv (&q)[K], const bool (&ok)[K], int cmp, int (&out)[K]) const
+    {
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            if (ok[k]) out[k] = subpel(q[k], cmp) + mvcost(q[k].x, q[k].y);
+    }
+
+    __device__ __forceinline__ void sea_search(Mv mvmin, Mv mvmax, int merange, Mv& bmv, int& bcost) const
+    {
+        // X265_SEA, motion.cpp:1242-1395.  A row of the window is one step: every lane forms the DC lower bound of its position (ads_x4 / x2 / x1,
+        // pixel.cpp:121-166: |sum of the PU's quarters - window sums of the reference| + the position's x cost) against the row-start best;
+        // a ballot is the list of survivors in x order; survivors are SAD-ed three at a time and compared in order (COST_MV_X3_ABS), the
+        // last one or two of the row with the ordinary cost (COST_MV).  The arithmetic is the reference's as it stands (see the oracle).
+        const int minX = max(bmv.x - merange, mvmin.x), minY = max(bmv.y - merange, mvmin.y);
+        const int maxX = min(bmv.x + merange, mvmax.x), maxY = min(bmv.y + merange, mvmax.y);
+        const int meRangeWidth = (maxX - minX + 3) & ~3;
+        int deltaX = w <= 8 ? w : w >> 1;
+        int64_t deltaY = h <= 8 ? h : h >> 1;
+        const int wh = (w << 8) | h;
+        auto is = [wh](int a, int b) { return wh == ((a << 8) | b); };
+        const bool isSmall = is(4, 4) || is(16, 12) || is(12, 16) || is(16, 4) || is(4, 16);
+        const bool isV = is(32, 64) || is(16, 32) || is(8, 16) || is(4, 8), isH = is(64, 32) || is(32, 16) || is(16, 8) || is(8, 4);
+        const bool isAsym = is(12, 16) || is(4, 16) || is(24, 32) || is(8, 32) || is(48, 64) || is(16, 64) || is(16, 12) || is(16, 4) || is(32, 24) ||
+                            is(32, 8) || is(64, 48) || is(64, 16);
+        int tw, th;
+        if (isV) { tw = w; th = h >> 1; }
+        else if (isH) { tw = w >> 1; th = h; }
+        else if (isAsym) { tw = isSmall ? w : w >> 1; th = isSmall ? h : h >> 1; }
+        else { tw = w <= 8 ? w : w >> 1; th = w <= 8 ? h : h >> 1; }
+        // sums of the four sub-blocks of the source PU (sad_x4 against zeros, :1306-1312); blocks that leave the PU (shapes for which the
+        // reference reads whatever its 64x64 source cache holds there) are clamped to the PU: those shapes have no defined result
+        int encDC[4];
+#pragma unroll 1
+        for (int k = 0; k < 4; k++)
+        {
+            const int ox = (k & 1) ? deltaX : 0, oy = (k & 2) ? (int)deltaY : 0;
+            int sum = 0;
+            for (int e = lane; e < tw * th; e += 64)
+            {
+                const int yy = min(oy + e / tw, h - 1), xx = min(ox + e % tw, w - 1);
+                sum += (int)fenc[yy * w + xx];
+            }
+            encDC[k] = uni(wave_sum(sum));
+        }
+        int plane;
+        switch (deltaX)
+        {
+        case 32: plane = (deltaY % 24 == 0) ? 1 : (deltaY == 8 ? 2 : 0); break;
+        case 24: plane = 3; break;
+        case 16: plane = (deltaY % 12 == 0) ? 5 : (deltaY == 4 ? 6 : 4); break;
+        case 12: plane = 7; break;
+        case 8: plane = deltaY == 32 ? 8 : 9; break;
+        case 4: plane = deltaY == 16 ? 10 : 11; break;
+        default: plane = 11; break;
+        }
+        const uint32_t* sumsBase = sea.base + (int64_t)plane * sea.planeElems + (int64_t)by * stride + bx;
+        const bool strided = is(64, 64) || is(32, 32) || is(16, 16) || is(32, 64) || is(16, 32) || is(8, 16) || is(4, 8) || is(12, 16) || is(4, 16) ||
+                             is(24, 32) || is(8, 32) || is(48, 64) || is(16, 64);
+        if (strided) deltaY *= stride;
+        if (isV) encDC[1] = encDC[2];
+        if (isH) deltaY = deltaX;
+        const int kind = (is(4, 4) || is(8, 8) || is(16, 12) || is(12, 16) || is(16, 4) || is(4, 16)) ? 1
+                       : ((is(8, 4) || is(4, 8) || is(16, 8) || is(8, 16) || is(32, 16) || is(16, 32) || is(64, 32) || is(32, 64)) ? 2 : 4);
+        const int chunks = (meRangeWidth + 63) >> 6;                 // <= 4: merange <= 126 (checked at the entry point)
+        Mv cand[4];
+        int costs[4];
+#pragma unroll 1
+        for (int ty = minY; ty <= maxY; ty++)
+        {
+            const int ycost = uni((int)cost[ty - 2 * qmvp.y]) << 2;
+            if (bcost <= ycost)
+                continue;
+            bcost -= ycost;
+            unsigned long long keep[4] = { 0, 0, 0, 0 };
+            const uint32_t* sums = sumsBase + minX + (int64_t)ty * stride;
+#pragma unroll
+            for (int ch = 0; ch < 4; ch++)
+            {
+                const int i = ch * 64 + lane;
+                bool k = false;
+                if (ch < chunks && i < meRangeWidth)
+                {
+                    long long a = llabs((long long)encDC[0] - (long long)sums[i]);
+                    if (kind == 4)
+                        a += llabs((long long)encDC[1] - (long long)sums[i + (w >> 1)]) + llabs((long long)encDC[2] - (long long)sums[i + deltaY]) +
+                             llabs((long long)encDC[3] - (long long)sums[i + deltaY + (w >> 1)]);
+                    else if (kind == 2)
+                        a += llabs((long long)encDC[1] - (long long)sums[i + deltaY]);
+                    k = (int)(a + cost[4 * (minX + i) - qmvp.x]) < bcost;
+                }
+                keep[ch] = __ballot(k);
+            }
+            // survivors in x order, three at a time
+            int px[3], np = 0;
+#pragma unroll 1
+            for (int ch = 0; ch < chunks; ch++)
+            {
+                unsigned long long m = keep[ch];
+                while (m)
+                {
+                    const int bit = __builtin_ctzll(m);
+                    m &= m - 1;
+                    px[np++] = minX + ch * 64 + bit;
+                    if (np == 3)
+                    {
+                        cand[0] = Mv{ px[0], ty }; cand[1] = Mv{ px[1], ty }; cand[2] = Mv{ px[2], ty }; cand[3] = cand[2];
+                        sad_multi(3, cand, costs);
+#pragma unroll
+                        for (int k3 = 0; k3 < 3; k3++)
+                        {
+                            const int cst = costs[k3] + uni((int)cost[4 * px[k3] - 2 * qmvp.x]);      // x cost only, predictor taken off twice (:307-309)
+                            if (cst < bcost) { bcost = cst; bmv.x = px[k3]; bmv.y = ty; }
+                        }
+                        np = 0;
+                    }
+                }
+            }
+            bcost += ycost;
+            for (int k3 = 0; k3 < np; k3++)                                                              // COST_MV
+            {
+                const int cst = sad_at(px[k3], ty) + mvcost(px[k3] * 4, ty * 4);
+                if (cst < bcost) { bcost = cst; bmv.x = px[k3]; bmv.y = ty; }
+            }
+        }
+    }
 };
-
-__device__ __forceinline__ Mv mv_clip(Mv v, Mv lo, Mv hi)
-{
-    Mv r = { v.x > hi.x ? hi.x : v.x, v.y > hi.y ? hi.y : v.y };
-    r.x = r.x < lo.x ? lo.x : r.x;
-    r.y = r.y < lo.y ? lo.y : r.y;
-    return r;
-}
-__device__ __forceinline__ bool mv_in_range(Mv v, Mv lo, Mv hi) { return v.x >= lo.x && v.x <= hi.x && v.y >= lo.y && v.y <= hi.y; }
-__device__ __forceinline__ int sext2(int v) { return (v & 2) ? (v | ~3) : v; }
-
-__device__ __constant__ const int8_t kHex2[8][2] = { {-1,-2}, {-2,0}, {-1,2}, {1,2}, {2,0}, {1,-2}, {-1,-2}, {-2,0} };   // motion.cpp:63
-__device__ __constant__ const uint8_t kMod6m1[8] = { 5, 0, 1, 2, 3, 4, 5, 0 };                                             // motion.cpp:64
-__device__ __constant__ const int8_t kSquare1[9][2] = { {0,0}, {0,-1}, {0,1}, {-1,0}, {1,0}, {-1,-1}, {-1,1}, {1,-1}, {1,1} }; // motion.cpp:65
-// motion.cpp:48-58 workload[subme] = { hpel_iters, hpel_dirs, qpel_iters, qpel_dirs, hpel_satd }
-__device__ __constant__ const uint8_t kWorkload[8][5] = { {1,4,0,4,0}, {1,4,1,4,0}, {1,4,1,4,1}, {2,4,1,4,1}, {2,4,2,4,1}, {1,8,1,8,1}, {2,8,1,8,1}, {2,8,2,8,1} };
 
 template <typename P>
 __global__ __launch_bounds__(256) void motion_kernel(const P* __restrict__ fencPlane, int64_t strideF,
@@ -344,6 +462,7 @@ __global__ __launch_bounds__(256) void motion_kernel(const P* __restrict__ fencP
     c.fencCr = c.fencCb + (w >> 1) * (h >> 1);
     c.stride = strideR;
     c.cost = mvcost;
+    c.sea = sea;
     typedef typename MeCtx<P>::Q Q;
 
     const int wavesPerWg = blockDim.x >> 6;
@@ -353,8 +472,9 @@ __global__ __launch_bounds__(256) void motion_kernel(const P* __restrict__ fencP
         const int bx = pu_xy[2 * pu], by = pu_xy[2 * pu + 1];
         const Mv mvmin = { mvminA[2 * pu], mvminA[2 * pu + 1] }, mvmax = { mvmaxA[2 * pu], mvmaxA[2 * pu + 1] };
         const Mv qmvp = { qmvpA[2 * pu], qmvpA[2 * pu + 1] };
-        const Mv qmvmin = { mvmin.x * 4, mvmin.y * 4 }, qmvmax = { mvmax.x * 4, mvmax.y * 4 };
         c.qmvp = qmvp;
+        c.bx = bx;
+        c.by = by;
         c.fref = refPlane + (int64_t)by * strideR + bx;
         // source block -> LDS
         {
@@ -381,352 +501,12 @@ __global__ __launch_bounds__(256) void motion_kernel(const P* __restrict__ fencP
             __builtin_amdgcn_wave_barrier();
         }
 
-#define YOK(yy) (((yy) >= mvmin.y) & ((yy) <= mvmax.y))
-#define LT1(v) do { const int v_ = (v); if (v_ < bcost) bcost = v_; } while (0)
-        // ---- predictor, zero and candidates (motion.cpp:761-812)
-        const Mv pmv = mv_clip(qmvp, qmvmin, qmvmax);
-        Mv bestpre = pmv;
-        int bprecost = c.subpel(pmv, 0);
-        Mv bmv = { (pmv.x + 2) >> 2, (pmv.y + 2) >> 2 };
-        int bcost = bprecost;
-        if ((pmv.x & 3) | (pmv.y & 3))
-            bcost = c.sad_at(bmv.x, bmv.y) + c.mvcost(bmv.x * 4, bmv.y * 4);
-        if (pmv.x | pmv.y)
-        {
-            const int cst = c.sad_at(0, 0) + c.mvcost(0, 0);
-            if (cst < bcost)
-            {
-                bcost = cst;
-                bmv.x = 0;
-                bmv.y = max(min(0, mvmax.y), mvmin.y);
-            }
-        }
-        for (int i = 0; i < numCand; i++)
-        {
-            const Mv raw = { mvcA[((int64_t)pu * numCand + i) * 2], mvcA[((int64_t)pu * numCand + i) * 2 + 1] };
-            const Mv m = mv_clip(raw, qmvmin, qmvmax);
-            if ((m.x | m.y) && !(m.x == pmv.x && m.y == pmv.y) && !(m.x == bestpre.x && m.y == bestpre.y))
-            {
-                const int cst = c.subpel(m, 0) + c.mvcost(m.x, m.y);
-                if (cst < bprecost)
-                {
-                    bprecost = cst;
-                    bestpre = m;
-                }
-            }
-        }
-
-        int costs[4];
-        Mv cand[4];
-#define DIRS3(ax, ay, bx_, by_, cx, cy) do { \
-            cand[0] = Mv{ bmv.x + (ax), bmv.y + (ay) }; cand[1] = Mv{ bmv.x + (bx_), bmv.y + (by_) }; cand[2] = Mv{ bmv.x + (cx), bmv.y + (cy) }; \
-            c.sad_multi(3, cand, costs); \
-            for (int k_ = 0; k_ < 3; k_++) costs[k_] += c.mvcost(cand[k_].x * 4, cand[k_].y * 4); } while (0)
-#define DIRS4(ax, ay, bx_, by_, cx, cy, dx, dy) do { \
-            cand[0] = Mv{ bmv.x + (ax), bmv.y + (ay) }; cand[1] = Mv{ bmv.x + (bx_), bmv.y + (by_) }; \
-            cand[2] = Mv{ bmv.x + (cx), bmv.y + (cy) }; cand[3] = Mv{ bmv.x + (dx), bmv.y + (dy) }; \
-            c.sad_multi(4, cand, costs); \
-            for (int k_ = 0; k_ < 4; k_++) costs[k_] += c.mvcost(cand[k_].x * 4, cand[k_].y * 4); } while (0)
-
-        // X265_UMH_SEARCH (meumh.h) ends either for good or in the hexagon refine of X265_HEX_SEARCH (goto me_hex2, motion.cpp:1127)
-        int meth = method, hexRange = merange;       // UMH scales the range the hexagon refine then runs with (motion.cpp:1039)
-        if (meth == 2)
-            meth = umh_search(c, mvmin.x, mvmin.y, mvmax.x, mvmax.y, hexRange, bmv.x, bmv.y, bcost, (pmv.x + 2) >> 2, (pmv.y + 2) >> 2, numCand,
-                              mvcA + (int64_t)pu * numCand * 2, qmvp.x, qmvp.y, w, h) ? 1 : -1;
-        if (meth == 0)
-        {
-            // X265_DIA_SEARCH, motion.cpp:831-852
-            bcost <<= 4;
-            int i = merange;
-            do
-            {
-                DIRS4(0, -1, 0, 1, -1, 0, 1, 0);
-                if (YOK(bmv.y - 1)) LT1((costs[0] << 4) + 1);
-                if (YOK(bmv.y + 1)) LT1((costs[1] << 4) + 3);
-                LT1((costs[2] << 4) + 4);
-                LT1((costs[3] << 4) + 12);
-                if (!(bcost & 15))
-                    break;
-                bmv.x -= sext2((bcost >> 2) & 3);
-                bmv.y -= sext2(bcost & 3);
-                bcost &= ~15;
-            }
-            while (--i && mv_in_range(bmv, mvmin, mvmax));
-            bcost >>= 4;
-        }
-        else if (meth == 1)
-        {
-            // X265_HEX_SEARCH, motion.cpp:855-944
-            DIRS3(-2, 0, -1, 2, 1, 2);
-            bcost <<= 3;
-            if (YOK(bmv.y)) LT1((costs[0] << 3) + 2);
-            if (YOK(bmv.y + 2))
-            {
-                LT1((costs[1] << 3) + 3);
-                LT1((costs[2] << 3) + 4);
-            }
-            DIRS3(2, 0, 1, -2, -1, -2);
-            if (YOK(bmv.y)) LT1((costs[0] << 3) + 5);
-            if (YOK(bmv.y - 2))
-            {
-                LT1((costs[1] << 3) + 6);
-                LT1((costs[2] << 3) + 7);
-            }
-            if (bcost & 7)
-            {
-                int dir = (bcost & 7) - 2;
-                if (YOK(bmv.y + kHex2[dir + 1][1]))
-                {
-                    bmv.x += kHex2[dir + 1][0];
-                    bmv.y += kHex2[dir + 1][1];
-                    for (int i = (hexRange >> 1) - 1; i > 0 && mv_in_range(bmv, mvmin, mvmax); i--)
-                    {
-                        DIRS3(kHex2[dir + 0][0], kHex2[dir + 0][1], kHex2[dir + 1][0], kHex2[dir + 1][1], kHex2[dir + 2][0], kHex2[dir + 2][1]);
-                        bcost &= ~7;
-                        if (YOK(bmv.y + kHex2[dir + 0][1])) LT1((costs[0] << 3) + 1);
-                        if (YOK(bmv.y + kHex2[dir + 1][1])) LT1((costs[1] << 3) + 2);
-                        if (YOK(bmv.y + kHex2[dir + 2][1])) LT1((costs[2] << 3) + 3);
-                        if (!(bcost & 7))
-                            break;
-                        dir += (bcost & 7) - 2;
-                        dir = kMod6m1[dir + 1];
-                        bmv.x += kHex2[dir + 1][0];
-                        bmv.y += kHex2[dir + 1][1];
-                    }
-                }
-            }
-            bcost >>= 3;
-            // square refine, motion.cpp:918-942
-            int dir = 0;
-            DIRS4(0, -1, 0, 1, -1, 0, 1, 0);
-            if (YOK(bmv.y - 1) && costs[0] < bcost) { bcost = costs[0]; dir = 1; }
-            if (YOK(bmv.y + 1) && costs[1] < bcost) { bcost = costs[1]; dir = 2; }
-            if (costs[2] < bcost) { bcost = costs[2]; dir = 3; }
-            if (costs[3] < bcost) { bcost = costs[3]; dir = 4; }
-            DIRS4(-1, -1, -1, 1, 1, -1, 1, 1);
-            if (YOK(bmv.y - 1) && costs[0] < bcost) { bcost = costs[0]; dir = 5; }
-            if (YOK(bmv.y + 1) && costs[1] < bcost) { bcost = costs[1]; dir = 6; }
-            if (YOK(bmv.y - 1) && costs[2] < bcost) { bcost = costs[2]; dir = 7; }
-            if (YOK(bmv.y + 1) && costs[3] < bcost) { bcost = costs[3]; dir = 8; }
-            bmv.x += kSquare1[dir][0];
-            bmv.y += kSquare1[dir][1];
-        }
-        else if (meth == 3)
-            star_search(c, mvmin.x, mvmin.y, mvmax.x, mvmax.y, merange, bmv.x, bmv.y, bcost);  // X265_STAR_SEARCH (mestar.h)
-        else if (meth == 4)
-        {
-            // X265_SEA, motion.cpp:1242-1395.  A row of the window is one step: every lane forms the DC lower bound of its position (ads_x4 / x2 / x1,
-            // pixel.cpp:121-166: |sum of the PU's quarters - window sums of the reference| + the position's x cost) against the row-start best;
-            // a ballot is the list of survivors in x order; survivors are SAD-ed three at a time and compared in order (COST_MV_X3_ABS), the
-            // last one or two of the row with the ordinary cost (COST_MV).  The arithmetic is the reference's as it stands (see the oracle).
-            const int minX = max(bmv.x - merange, mvmin.x), minY = max(bmv.y - merange, mvmin.y);
-            const int maxX = min(bmv.x + merange, mvmax.x), maxY = min(bmv.y + merange, mvmax.y);
-            const int meRangeWidth = (maxX - minX + 3) & ~3;
-            int deltaX = w <= 8 ? w : w >> 1;
-            int64_t deltaY = h <= 8 ? h : h >> 1;
-            const int wh = (w << 8) | h;
-            auto is = [wh](int a, int b) { return wh == ((a << 8) | b); };
-            const bool isSmall = is(4, 4) || is(16, 12) || is(12, 16) || is(16, 4) || is(4, 16);
-            const bool isV = is(32, 64) || is(16, 32) || is(8, 16) || is(4, 8), isH = is(64, 32) || is(32, 16) || is(16, 8) || is(8, 4);
-            const bool isAsym = is(12, 16) || is(4, 16) || is(24, 32) || is(8, 32) || is(48, 64) || is(16, 64) || is(16, 12) || is(16, 4) || is(32, 24) ||
-                                is(32, 8) || is(64, 48) || is(64, 16);
-            int tw, th;
-            if (isV) { tw = w; th = h >> 1; }
-            else if (isH) { tw = w >> 1; th = h; }
-            else if (isAsym) { tw = isSmall ? w : w >> 1; th = isSmall ? h : h >> 1; }
-            else { tw = w <= 8 ? w : w >> 1; th = w <= 8 ? h : h >> 1; }
-            // sums of the four sub-blocks of the source PU (sad_x4 against zeros, :1306-1312); blocks that leave the PU (shapes for which the
-            // reference reads whatever its 64x64 source cache holds there) are clamped to the PU: those shapes have no defined result
-            int encDC[4];
-#pragma unroll 1
-            for (int k = 0; k < 4; k++)
-            {
-                const int ox = (k & 1) ? deltaX : 0, oy = (k & 2) ? (int)deltaY : 0;
-                int sum = 0;
-                for (int e = c.lane; e < tw * th; e += 64)
-                {
-                    const int yy = min(oy + e / tw, h - 1), xx = min(ox + e % tw, w - 1);
-                    sum += (int)c.fenc[yy * w + xx];
-                }
-                encDC[k] = uni(wave_sum(sum));
-            }
-            int plane;
-            switch (deltaX)
-            {
-            case 32: plane = (deltaY % 24 == 0) ? 1 : (deltaY == 8 ? 2 : 0); break;
-            case 24: plane = 3; break;
-            case 16: plane = (deltaY % 12 == 0) ? 5 : (deltaY == 4 ? 6 : 4); break;
-            case 12: plane = 7; break;
-            case 8: plane = deltaY == 32 ? 8 : 9; break;
-            case 4: plane = deltaY == 16 ? 10 : 11; break;
-            default: plane = 11; break;
-            }
-            const uint32_t* sumsBase = sea.base + (int64_t)plane * sea.planeElems + (int64_t)by * strideR + bx;
-            const bool strided = is(64, 64) || is(32, 32) || is(16, 16) || is(32, 64) || is(16, 32) || is(8, 16) || is(4, 8) || is(12, 16) || is(4, 16) ||
-                                 is(24, 32) || is(8, 32) || is(48, 64) || is(16, 64);
-            if (strided) deltaY *= strideR;
-            if (isV) encDC[1] = encDC[2];
-            if (isH) deltaY = deltaX;
-            const int kind = (is(4, 4) || is(8, 8) || is(16, 12) || is(12, 16) || is(16, 4) || is(4, 16)) ? 1
-                           : ((is(8, 4) || is(4, 8) || is(16, 8) || is(8, 16) || is(32, 16) || is(16, 32) || is(64, 32) || is(32, 64)) ? 2 : 4);
-            const int chunks = (meRangeWidth + 63) >> 6;                 // <= 4: merange <= 126 (checked at the entry point)
-#pragma unroll 1
-            for (int ty = minY; ty <= maxY; ty++)
-            {
-                const int ycost = uni((int)c.cost[ty - 2 * qmvp.y]) << 2;
-                if (bcost <= ycost)
-                    continue;
-                bcost -= ycost;
-                unsigned long long keep[4] = { 0, 0, 0, 0 };
-                const uint32_t* sums = sumsBase + minX + (int64_t)ty * strideR;
-#pragma unroll
-                for (int ch = 0; ch < 4; ch++)
-                {
-                    const int i = ch * 64 + c.lane;
-                    bool k = false;
-                    if (ch < chunks && i < meRangeWidth)
-                    {
-                        long long a = llabs((long long)encDC[0] - (long long)sums[i]);
-                        if (kind == 4)
-                            a += llabs((long long)encDC[1] - (long long)sums[i + (w >> 1)]) + llabs((long long)encDC[2] - (long long)sums[i + deltaY]) +
-                                 llabs((long long)encDC[3] - (long long)sums[i + deltaY + (w >> 1)]);
-                        else if (kind == 2)
-                            a += llabs((long long)encDC[1] - (long long)sums[i + deltaY]);
-                        k = (int)(a + c.cost[4 * (minX + i) - qmvp.x]) < bcost;
-                    }
-                    keep[ch] = __ballot(k);
-                }
-                // survivors in x order, three at a time
-                int px[3], np = 0;
-#pragma unroll 1
-                for (int ch = 0; ch < chunks; ch++)
-                {
-                    unsigned long long m = keep[ch];
-                    while (m)
-                    {
-                        const int bit = __builtin_ctzll(m);
-                        m &= m - 1;
-                        px[np++] = minX + ch * 64 + bit;
-                        if (np == 3)
-                        {
-                            cand[0] = Mv{ px[0], ty }; cand[1] = Mv{ px[1], ty }; cand[2] = Mv{ px[2], ty }; cand[3] = cand[2];
-                            c.sad_multi(3, cand, costs);
-#pragma unroll
-                            for (int k3 = 0; k3 < 3; k3++)
-                            {
-                                const int cst = costs[k3] + uni((int)c.cost[4 * px[k3] - 2 * qmvp.x]);      // x cost only, predictor taken off twice (:307-309)
-                                if (cst < bcost) { bcost = cst; bmv.x = px[k3]; bmv.y = ty; }
-                            }
-                            np = 0;
-                        }
-                    }
-                }
-                bcost += ycost;
-                for (int k3 = 0; k3 < np; k3++)                                                              // COST_MV
-                {
-                    const int cst = c.sad_at(px[k3], ty) + c.mvcost(px[k3] * 4, ty * 4);
-                    if (cst < bcost) { bcost = cst; bmv.x = px[k3]; bmv.y = ty; }
-                }
-            }
-        }
-        else if (meth == 5)
-        {
-            // X265_FULL_SEARCH, motion.cpp:1397-1441: raster order, strict '<' keeps the first minimum
-            for (int ty = mvmin.y; ty <= mvmax.y; ty++)
-                for (int tx = mvmin.x; tx <= mvmax.x; tx += 4)
-                {
-                    const int K = min(4, mvmax.x - tx + 1);
-                    for (int k = 0; k < 4; k++)
-                        cand[k] = Mv{ tx + min(k, K - 1), ty };
-                    c.sad_multi(K, cand, costs);
-                    for (int k = 0; k < K; k++)
-                    {
-                        const int cst = costs[k] + c.mvcost((tx + k) * 4, ty * 4);
-                        if (cst < bcost)
-                        {
-                            bcost = cst;
-                            bmv.x = tx + k;
-                            bmv.y = ty;
-                        }
-                    }
-                }
-        }
-
-        // motion.cpp:1449-1455
-        if (bprecost < bcost)
-        {
-            bmv = bestpre;
-            bcost = bprecost;
-        }
-        else
-        {
-            bmv.x *= 4;
-            bmv.y *= 4;
-        }
-
-        if (!bcost)
-            bcost = c.mvcost(bmv.x, bmv.y);            // motion.cpp:1466-1471
-        else
-        {
-            // motion.cpp:1504-1561
-            const int hpelIters = kWorkload[subme][0], hpelDirs = kWorkload[subme][1];
-            const int qpelIters = kWorkload[subme][2], qpelDirs = kWorkload[subme][3], hpelSatd = kWorkload[subme][4];
-            int hpelcomp = 0;
-            if (hpelSatd)
-            {
-                bcost = c.subpel(bmv, 1) + c.mvcost(bmv.x, bmv.y);
-                hpelcomp = 1;
-            }
-            for (int iter = 0; iter < hpelIters; iter++)
-            {
-                int bdir = 0;
-                for (int i = 1; i <= hpelDirs; i++)
-                {
-                    const Mv q = { bmv.x + kSquare1[i][0] * 2, bmv.y + kSquare1[i][1] * 2 };
-                    if ((q.y < qmvmin.y) | (q.y > qmvmax.y))
-                        continue;
-                    const int cst = c.subpel(q, hpelcomp) + c.mvcost(q.x, q.y);
-                    if (cst < bcost) { bcost = cst; bdir = i; }
-                }
-                if (bdir)
-                {
-                    bmv.x += kSquare1[bdir][0] * 2;
-                    bmv.y += kSquare1[bdir][1] * 2;
-                }
-                else
-                    break;
-            }
-            if (!hpelSatd)
-                bcost = c.subpel(bmv, 1) + c.mvcost(bmv.x, bmv.y);
-            for (int iter = 0; iter < qpelIters; iter++)
-            {
-                int bdir = 0;
-                for (int i = 1; i <= qpelDirs; i++)
-                {
-                    const Mv q = { bmv.x + kSquare1[i][0], bmv.y + kSquare1[i][1] };
-                    if ((q.y < qmvmin.y) | (q.y > qmvmax.y))
-                        continue;
-                    const int cst = c.subpel(q, 1) + c.mvcost(q.x, q.y);
-                    if (cst < bcost) { bcost = cst; bdir = i; }
-                }
-                if (bdir)
-                {
-                    bmv.x += kSquare1[bdir][0];
-                    bmv.y += kSquare1[bdir][1];
-                }
-                else
-                    break;
-            }
-        }
-#undef YOK
-#undef LT1
-#undef DIRS3
-#undef DIRS4
+        const MeBest best = me_search(c, qmvp, mvmin, mvmax, numCand, mvcA + (int64_t)pu * numCand * 2, merange, method, subme, w, h);
         if (c.lane == 0)
         {
-            outMv[2 * pu] = bmv.x;
-            outMv[2 * pu + 1] = bmv.y;
-            outCost[pu] = bcost;
+            outMv[2 * pu] = best.mv.x;
+            outMv[2 * pu + 1] = best.mv.y;
+            outCost[pu] = best.cost;
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
@@ -736,13 +516,6 @@ __global__ __launch_bounds__(256) void motion_kernel(const P* __restrict__ fencP
 } // namespace xh
 
 using namespace xh;
-
-namespace xh {
-int motion2_dispatch(int depth, int w, int h, const void* fencPlane, int64_t strideF, const void* refPlane, int64_t strideR,
-                     const int32_t* pu_xy, const int32_t* mvmin, const int32_t* mvmax, const int32_t* qmvp, int numCand,
-                     const int32_t* mvc, int merange, int method, int subme, const uint16_t* mvcost, int n, const void* planes,
-                     int64_t planeElems, int32_t* outMv, int32_t* outCost, hipStream_t st, int* rc, const DeriveRange* drp = nullptr);
-}
 
 extern "C" int x265hip_motion_estimate_batch(int depth, int w, int h, const void* fencPlane, int64_t strideF,
                                              const void* refPlane, int64_t strideR, const int32_t* pu_xy,
@@ -802,12 +575,17 @@ extern "C" int x265hip_motion_estimate_planes_batch(int depth, int w, int h, con
     int e = check_me_args("motion_estimate", depth, w, h, n, searchMethod, subme, numCand, merange, mvcostHalf);
     if (e) return e;
     if (!n) return X265HIP_OK;
-    // square 8..64 PUs run on the team kernel of motion2.hip; everything else (and X265HIP_ME_V1=1) on the generic one
-    static const bool forceV1 = getenv("X265HIP_ME_V1") != nullptr;
-    int rc2 = 0;
-    if (!forceV1 && motion2_dispatch(depth, w, h, fencPlane, strideF, refPlane, strideR, pu_xy, mvmin, mvmax, qmvp, numCand, mvc, merange,
-                                     searchMethod, subme, mvcost, n, subpelPlanes, planeElems, outMv, outCost, as_stream(stream), &rc2))
-        return rc2;
+    switch (me_kernel_for(w, h, subpelPlanes, strideR))
+    {
+    case ME_ROW_TEAM:
+        return launch_motion3(depth, w, fencPlane, strideF, strideR, pu_xy, mvmin, mvmax, qmvp, numCand, mvc, merange, searchMethod, subme, mvcost, n,
+                              subpelPlanes, planeElems, DeriveRange{}, ChromaPlanes{}, outMv, outCost, as_stream(stream));
+    case ME_TEAM:
+        return launch_motion2(depth, w, fencPlane, strideF, refPlane, strideR, pu_xy, mvmin, mvmax, qmvp, numCand, mvc, merange, searchMethod, subme,
+                              mvcost, n, subpelPlanes, planeElems, DeriveRange{}, outMv, outCost, as_stream(stream));
+    default:
+        break;
+    }
     const ChromaPlanes none{};
     return launch_motion_v1(depth, w, h, fencPlane, strideF, refPlane, strideR, pu_xy, mvmin, mvmax, qmvp, numCand, mvc, merange, searchMethod,
                             subme, mvcost, n, outMv, outCost, none, as_stream(stream));
