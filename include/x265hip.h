@@ -831,22 +831,26 @@ int x265hip_call_frame_init_lowres(int depth, const void* src, int64_t srcStride
 /* One job = the transform arithmetic of one inter CU's residual quad-tree, everything Search::estimateResidualQT (reference
  * source/encoder/search.cpp:3178-3560) asks of Quant::transformNxN (common/quant.cpp:397-470: cu[].dct -> quant -> signBitHidingHDQ
  * :246-395) and Quant::invtransformNxN (:543-603: dequant_normal -> cu[].idct) for the luma transform sizes 32 and 16 the tree may
- * try (4:2:0 chroma 16 and 8), plus the two sse_pp distortions of every unit (search.cpp:3269, :3295).  The caller (x265_amd/host/
+ * try (chroma 16 and 8 at 4:2:0 and 4:2:2, 32 and 16 at 4:4:4), plus the two sse_pp distortions of every unit (search.cpp:3269, :3295).  The caller (x265_amd/host/
  * x265_hip_cuserve.cpp) keeps the entropy coder and every decision.  Jobs travel through mailbox SLOTS in page-locked host memory
  * that the device reads and writes directly: the caller fills the slot's job header and pixel block, submits, and polls the
  * per-unit `ready` / `readyInv` words (each unit's forward half — numSig and levels — is published as soon as it is done, luma first;
  * its inverse half follows).  Flat quantiser only (no scaling lists), no
  * transform skip, no transquant bypass, no noise reduction, no RDOQ: the caller does not submit such CUs.
  *
- * Pixel block: source Y (N x N, N = 1 << log2CUSize), source Cb, Cr (N/2 x N/2 each, 4:2:0; absent when chroma == 0), then the
+ * Chroma format of a job (x265hip_cujob::chroma, the values of X265_CSP_I400..I444) and its chroma shifts hs / vs: 0 no chroma, 1 4:2:0 (1 / 1),
+ * 2 4:2:2 (1 / 0), 3 4:4:4 (0 / 0); x265hip_cujob_formats() tells which of them the library accepts.
+ * Pixel block: source Y (N x N, N = 1 << log2CUSize), source Cb, Cr ((N >> hs) wide, (N >> vs) tall each; absent when chroma == 0), then the
  * prediction in the same order; rows contiguous; elements uint8_t (bitDepth 8) or uint16_t.
  * Levels: luma transform sizes s from sHi = min(5, log2TrMax, log2CUSize) down to sLo = max(4, log2TrMin); no level when sHi < sLo.
- * Units of a level: plane 0 (Y), then 1 (Cb), 2 (Cr); within a plane raster order of the (N >> s)^2 units. */
+ * Units of a level: plane 0 (Y), then 1 (Cb), 2 (Cr); within a plane raster order of its units: (N >> s)^2 luma units of size s; a chroma plane holds
+ * (N >> hs >> (s - hs)) x (N >> vs >> (s - hs)) units of size s - hs.  At 4:2:2 that is n x 2n units (n = N >> s): the two square sub-TUs of the
+ * reference's transform unit (tuX, tuY) (search.cpp:3251, :3388-3393) are rows 2 * tuY and 2 * tuY + 1. */
 typedef struct x265hip_cujob
 {
     uint32_t log2CUSize;          /* 4..6 */
     uint32_t log2TrMax, log2TrMin;/* the luma transform sizes the tree may try (Search::estimateResidualQT's depthRange, largest first) */
-    uint32_t chroma;              /* 1: 4:2:0 Cb and Cr blocks are part of the job */
+    uint32_t chroma;              /* the chroma format: 0 luma alone, 1 4:2:0, 2 4:2:2, 3 4:4:4: Cb and Cr blocks are part of the job */
     uint32_t bitDepth;            /* 8, 10, 12 */
     uint32_t quantOffset;         /* 171 (I slice) or 85: quant.cpp:466 `add = offset << (qbits - 9)` */
     uint32_t signHide;            /* pps->bSignHideEnabled: signBitHidingHDQ runs on units with numSig >= 2 */
@@ -879,9 +883,9 @@ typedef struct x265hip_cujob_unit
     uint32_t reserved[3];         /* diagnostic (job.reserved != 0): 16-bit 100 MHz ticks since the job's start, low | high half: [0] chain starts | forward transform
                                    * done, [1] quantised | sign hiding done, [2] inverse transform done | readyInv issued */
 } x265hip_cujob_unit;
-#define X265HIP_CUJOB_MAX_UNITS   60                       /* 64x64, sizes 32 + 16: 3 * (4 + 16) */
-#define X265HIP_CUJOB_MAX_ELEMS   (2 * 6144)               /* int16 entries of `levels` (and of `resi`) of the largest job */
-#define X265HIP_CUJOB_PIXEL_BYTES (2 * 6144 * 2)           /* source + prediction of a 64x64 4:2:0 CU at 16 bit */
+#define X265HIP_CUJOB_MAX_UNITS   100                      /* 4:2:2, 64x64, sizes 32 + 16: (1 + 2 * 2) * (4 + 16) */
+#define X265HIP_CUJOB_MAX_ELEMS   (2 * 12288)              /* int16 entries of `levels` (and of `resi`) of the largest job: 4:4:4, 64x64, two levels */
+#define X265HIP_CUJOB_PIXEL_BYTES (2 * 12288 * 2)          /* source + prediction of a 64x64 4:4:4 CU at 16 bit */
 /* inline layout helpers (x265hipi_*: not exported symbols) shared by the library, the bindings and the checkers */
 #if defined(__HIPCC__)
 #define X265HIP_HD __host__ __device__
@@ -895,27 +899,37 @@ X265HIP_HD static inline int x265hipi_cujob_levels(const x265hip_cujob* j, int* 
     *sHi = hi; *sLo = lo;
     return hi - lo + 1;
 }
-/* index of unit (s, plane, tuX, tuY) in the slot's `units` array; s = log2 of the LUMA transform size of the level */
+/* the chroma shifts of format `chroma` (1..3), and the units of ONE chroma plane per luma unit of a level (2 at 4:2:2, 0 without chroma) */
+X265HIP_HD static inline int x265hipi_cujob_hshift(uint32_t chroma) { return chroma == 3 ? 0 : 1; }
+X265HIP_HD static inline int x265hipi_cujob_vshift(uint32_t chroma) { return chroma == 1 ? 1 : 0; }
+X265HIP_HD static inline int x265hipi_cujob_chroma_units(uint32_t chroma) { return chroma == 2 ? 2 : chroma ? 1 : 0; }
+/* samples of one chroma plane of an N x N CU (N2 = N * N) */
+X265HIP_HD static inline int x265hipi_cujob_chroma_elems(uint32_t chroma, int N2) { return chroma ? N2 >> (3 - (int)chroma) : 0; }
+/* index of unit (s, plane, tuX, tuY) in the slot's `units` array; s = log2 of the LUMA transform size of the level; (tuX, tuY) = the unit's place in the raster
+ * of ITS plane (a 4:2:2 chroma plane has twice as many rows of units as columns) */
 X265HIP_HD static inline int x265hipi_cujob_unit_index(const x265hip_cujob* j, int sHi, int s, int plane, int tuX, int tuY)
 {
-    const int planes = j->chroma ? 3 : 1;
+    const int cu = x265hipi_cujob_chroma_units(j->chroma);
     int base = 0;
     for (int k = sHi; k > s; k--)
-        base += planes << (2 * ((int)j->log2CUSize - k));
+        base += (1 + 2 * cu) << (2 * ((int)j->log2CUSize - k));
     const int n = 1 << ((int)j->log2CUSize - s);
-    return base + plane * n * n + tuY * n + tuX;
+    if (plane) base += n * n * (1 + (plane - 1) * cu);
+    return base + tuY * n + tuX;
 }
 /* offset (int16 entries) of the same unit's block in the slot's `levels` and `resi` arrays: (size of the unit)^2 entries, rows contiguous */
 X265HIP_HD static inline int x265hipi_cujob_elem_offset(const x265hip_cujob* j, int sHi, int s, int plane, int tuX, int tuY)
 {
     const int N2 = 1 << (2 * (int)j->log2CUSize), n = 1 << ((int)j->log2CUSize - s);
-    const int perLevel = j->chroma ? N2 + N2 / 2 : N2;
+    const int cElems = x265hipi_cujob_chroma_elems(j->chroma, N2);
     const int t = tuY * n + tuX;
-    int off = (sHi - s) * perLevel;
+    int off = (sHi - s) * (N2 + 2 * cElems);
     if (plane == 0) return off + (t << (2 * s));
-    off += N2 + (plane == 2 ? N2 / 4 : 0);
-    return off + (t << (2 * (s - 1)));
+    off += N2 + (plane == 2 ? cElems : 0);
+    return off + (t << (2 * (s - x265hipi_cujob_hshift(j->chroma))));
 }
+/* the chroma formats this library's CU jobs accept: bit f set for x265hip_cujob::chroma == f (0xF here).  Needs no device. */
+uint32_t x265hip_cujob_formats(void);
 typedef struct x265hip_cuserve x265hip_cuserve;
 /* mode 0: a resident server kernel per slot group polls the slots' doorbells (started on demand, ends by itself after `idle
  * microseconds` without work so that nothing in the process ever waits on it for long); mode 1: one launch per job on the slot's own

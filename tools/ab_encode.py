@@ -44,13 +44,17 @@ def main():
     ap.add_argument("--extra", default="--me hex")
     ap.add_argument("--out", default=None)
     ap.add_argument("--bits", type=int, default=8, help="encoder build: 8, 10 or 12 (x265_<bits>bit / x265_hip_<bits>bit); the clip stays 8-bit input")
+    ap.add_argument("--csp", default="i420", help="chroma format of the clip and the encode: i420, i422, i444 (--input-csp)")
+    ap.add_argument("--input-depth", type=int, default=8, help="10: the clip holds 16-bit samples with 10 significant bits")
     a = ap.parse_args()
     w, h = map(int, a.res.split("x"))
     from x265_amd.synth import make_clip
-    clip = "/tmp/ab_clip_%dx%d_%d.yuv" % (w, h, a.frames)
+    other = a.csp != "i420" or a.input_depth != 8
+    clip = "/tmp/ab_clip_%dx%d_%d%s.yuv" % (w, h, a.frames, "_%s_d%d" % (a.csp, a.input_depth) if other else "")
     if not os.path.exists(clip):
-        make_clip(clip, w, h, a.frames, seed=4321)
-    args = ["--input", clip, "--input-res", a.res, "--input-depth", "8", "--fps", "30", "--frames", str(a.frames), "--preset", a.preset, "--hash", "1"] + a.extra.split()
+        make_clip(clip, w, h, a.frames, seed=4321, csp=a.csp, depth=a.input_depth)
+    args = ["--input", clip, "--input-res", a.res, "--input-depth", str(a.input_depth), "--fps", "30", "--frames", str(a.frames), "--preset", a.preset, "--hash", "1"]
+    args += (["--input-csp", a.csp] if a.csp != "i420" else []) + a.extra.split()
     ref = run(os.path.join(REF, "x265_%dbit" % a.bits), args, "/tmp/ab_ref.hevc", dict(os.environ))
     cfgs = []
     for c in a.configs:
@@ -68,7 +72,7 @@ def main():
                 res[name].append(run(os.path.join(REF, "x265_vec_8bit"), args + ["--asm", "SSE4.1"], "/tmp/ab_%s.hevc" % name, e))
             else:
                 res[name].append(run(os.path.join(INTEG, "x265_hip_%dbit" % a.bits), args, "/tmp/ab_%s.hevc" % name, e))
-    summary = {"clip": "%s %d frames preset %s %s" % (a.res, a.frames, a.preset, a.extra), "reference": {"fps": ref["fps"], "user": round(ref["user"], 1)}, "configs": {}}
+    summary = {"clip": "%s %s %d-bit input, %d-bit build, %d frames preset %s %s" % (a.res, a.csp, a.input_depth, a.bits, a.frames, a.preset, a.extra), "reference": {"fps": ref["fps"], "user": round(ref["user"], 1)}, "configs": {}}
     print("reference: %.2f fps, user %.1f s" % (ref["fps"], ref["user"]))
     for name, env in cfgs:
         f = [x["fps"] for x in res[name] if x["fps"]]

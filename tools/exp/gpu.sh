@@ -106,11 +106,11 @@ PY
     pmc)
       HERE=$PWD
       for shape in cu5 cu6 sao; do for c in fetch:FETCH_SIZE write:WRITE_SIZE; do
-        (cd /tmp && export TMPDIR=/tmp && CUSERVE_RT_ONLY=$shape CUSERVE_RT_THREADS=1 timeout 200 rocprofv3 --pmc ${c#*:} --kernel-trace --output-format csv -d $HERE/$OUT/pmc/${shape}_${c%%:*} -o p -- $HERE/tools/micro/cuserve_rt 1 400 0 > $HERE/$OUT/pmc_${shape}_${c%%:*}.log 2>&1)
+        (cd /tmp && export TMPDIR=/tmp && CUSERVE_RT_ONLY=$shape CUSERVE_RT_THREADS=1 timeout 200 rocprofv3 --pmc ${c#*:} --kernel-trace --output-format csv -d $HERE/$OUT/pmc/${shape}_${c%%:*} -o p -- $HERE/tools/micro/cuserve_rt 1 400 0 > $HERE/$OUT/pmc_${shape}_${c%%:*}.log 2>&1) || { echo "pmc: pass $shape ${c#*:} failed, stopping"; exit 1; }
       done; done
       # the resident server (one dispatch for the whole run, idle polling included): 3100 jobs of one shape from one thread
       for c in fetch:FETCH_SIZE write:WRITE_SIZE; do
-        (cd /tmp && export TMPDIR=/tmp && CUSERVE_RT_ONLY=cu5 CUSERVE_RT_THREADS=1 timeout 200 rocprofv3 --pmc ${c#*:} --kernel-trace --output-format csv -d $HERE/$OUT/pmc/srv5_${c%%:*} -o p -- $HERE/tools/micro/cuserve_rt 0 3000 0 > $HERE/$OUT/pmc_srv5_${c%%:*}.log 2>&1)
+        (cd /tmp && export TMPDIR=/tmp && CUSERVE_RT_ONLY=cu5 CUSERVE_RT_THREADS=1 timeout 200 rocprofv3 --pmc ${c#*:} --kernel-trace --output-format csv -d $HERE/$OUT/pmc/srv5_${c%%:*} -o p -- $HERE/tools/micro/cuserve_rt 0 3000 0 > $HERE/$OUT/pmc_srv5_${c%%:*}.log 2>&1) || { echo "pmc: pass srv5 ${c#*:} failed, stopping"; exit 1; }
       done
       # algorithmic bytes: pixels in; levels + residual + unit records out (CU jobs), 480 statistics words out (SAO)
       python tools/prof/pmc_launches.py $OUT/pmc cu5:3200:6240 cu6:12416:24960 sao:12675:1920 srv5:3200:6240:3100 | tee $OUT/cuserve_pmc_per_job.txt ;;

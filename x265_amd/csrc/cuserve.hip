@@ -134,14 +134,20 @@ struct JobLds
 static_assert(sizeof(x265hip_cujob) <= 128, "job header");
 
 // ticket = what the host rings and the units' ready words take: bits 31..8 a running number (never 0, never 0xffffff), bits 7..0 what the device
-// needs to know before it has read anything: log2CUSize - 4 (bits 1..0), chroma (bit 2), 16-bit samples (bit 3), an inverse job's levels block (bit 4)
+// needs to know before it has read anything: log2CUSize - 4 (bits 1..0), chroma (bit 2), 16-bit samples (bit 3), an inverse job's levels block (bit 4),
+// the chroma format beyond 4:2:0 (bits 6..5: x265hip_cujob::chroma - 1 of a job with chroma, so 4:2:0 and 4:0:0 tickets are what they always were)
 // bits 1..0 == 3: an SAO statistics job (x265hip_saojob): bits 7..2 = the job's size, header included, in 512-byte steps
+__host__ __device__ inline uint32_t ticket_format(uint32_t t) { return (t & 4) ? 1 + ((t >> 5) & 3) : 0; }      // x265hip_cujob::chroma of a CU job's ticket
 __host__ __device__ inline uint32_t ticket_bytes(uint32_t t)
 {
     if ((t & 3) == 3) return ((t >> 2) & 63u) * 512u - 128u;
-    const uint32_t n2 = 1u << (2 * ((t & 3) + 4)), elems = (t & 4) ? n2 + n2 / 2 : n2;
+    const uint32_t n2 = 1u << (2 * ((t & 3) + 4)), elems = n2 + 2 * (uint32_t)x265hipi_cujob_chroma_elems(ticket_format(t), (int)n2);
     return 2 * elems * ((t & 8) ? 2 : 1);
 }
+// an SAO statistics job's pixel block ends inside the first 24 576 bytes of the slot's (what a 64x64 4:2:0 CU at 16 bit fills): its ticket's size field holds 63
+// steps of 512 bytes (a 64th would spill into the running number), so the CU jobs' larger blocks change nothing for these jobs
+constexpr int kSaoPixelBytes = 2 * 6144 * 2;
+static_assert(kSaoPixelBytes <= X265HIP_CUJOB_PIXEL_BYTES && (128 + kSaoPixelBytes) / 512 <= 63, "SAO statistics job: pixel block, ticket size field");
 
 struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal; };
 
@@ -164,7 +170,8 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
 }
 
 // One tile: units u0 .. u0 + G - 1 (G = (32 / N)^2, raster order, `count` of them exist) of size N x N of one plane.
-//   src / prd: the plane's source and prediction in LDS, `pw` elements per row; the plane has (pw / N)^2 units
+//   src / prd: the plane's source and prediction in LDS, `pw` elements per row; the plane has pw / N units per row (as many rows of them as the caller counts:
+//   pw / N, twice that for a 4:2:2 chroma plane)
 template <typename P, int N>
 __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64], const P* src, const P* prd, int pw, int u0, int count, const PlaneParams qp,
                                            bool signHide, x265hip_cujob_unit* units, int unitBase, int16_t* levels, int16_t* resi, int elemBase, uint32_t seq, uint64_t t0, bool stamps,
@@ -1243,8 +1250,10 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
 {
     const int wv = threadIdx.x >> 6;
     const x265hip_cujob& j = L.job;
-    const int N = 1 << j.log2CUSize, NC = N >> 1;
-    const int lumaElems = N * N, planeElems = j.chroma ? lumaElems + lumaElems / 2 : lumaElems;
+    // the chroma format (x265hip_cujob::chroma; the ticket carries it too, run_job): a chroma plane is N >> hs wide and N >> vs tall, its units of a level one
+    // size below the luma units' unless hs == 0
+    const int N = 1 << j.log2CUSize, hs = x265hipi_cujob_hshift(j.chroma), NC = N >> hs;
+    const int lumaElems = N * N, chromaElems = x265hipi_cujob_chroma_elems(j.chroma, lumaElems), planeElems = lumaElems + 2 * chromaElems;
     const P* src = reinterpret_cast<const P*>(L.pix);
     const P* prd = src + planeElems;
     if (j.coefMode == X265HIP_CUJOB_INVERSE)
@@ -1259,14 +1268,15 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
     for (int lv = 0; lv < levels; lv++)
     {
         const int sz = sHi - lv;
-        const int perRow = 1 << ((int)j.log2CUSize - sz), nUnits = perRow * perRow;
+        const int perRow = 1 << ((int)j.log2CUSize - sz);
         for (int plane = role ? 1 : 0; plane < (role ? (j.chroma ? 3 : 1) : 1); plane++)
         {
-            const int log2n = plane ? sz - 1 : sz;                          // 5, 4 (luma) or 4, 3 (chroma)
+            const int log2n = plane ? sz - hs : sz;                         // 5, 4 (luma, 4:4:4 chroma) or 4, 3 (4:2:0 and 4:2:2 chroma)
+            const int nUnits = perRow * perRow * (plane ? x265hipi_cujob_chroma_units(j.chroma) : 1);      // (4:2:2: twice as many rows of units)
             const int G = 1 << (2 * (5 - log2n));
             const int tiles = (nUnits + G - 1) / G;
-            const P* ps = plane == 0 ? src : plane == 1 ? src + lumaElems : src + lumaElems + lumaElems / 4;
-            const P* pp = plane == 0 ? prd : plane == 1 ? prd + lumaElems : prd + lumaElems + lumaElems / 4;
+            const P* ps = plane == 0 ? src : plane == 1 ? src + lumaElems : src + lumaElems + chromaElems;
+            const P* pp = plane == 0 ? prd : plane == 1 ? prd + lumaElems : prd + lumaElems + chromaElems;
             const int pw = plane ? NC : N;
             const PlaneParams qp = plane_params(j, plane, log2n);
             // coefficient mode: a luma tile whose source block is wanted as well is TWO work items (residual part, source part)
@@ -1629,11 +1639,12 @@ __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L
     }
     else
     {
-        // header (8 chunks), then the role's planes of the source and of the prediction: luma n2 * B bytes at 0, chroma n2 / 2 * B bytes behind it, the
-        // prediction planeBytes further on (all multiples of 16)
+        // header (8 chunks), then the role's planes of the source and of the prediction: luma n2 * B bytes at 0, both chroma planes (c2 * B bytes, by the
+        // ticket's format: n2 / 2, n2 or 2 * n2 samples) behind it, the prediction planeBytes further on (all multiples of 16)
         const int B = (ticket & 8) ? 2 : 1, n2 = 1 << (2 * ((int)(ticket & 3) + 4));
-        const int planeBytes = ((ticket & 4) ? n2 + n2 / 2 : n2) * B;
-        const int first = (role ? n2 * B : 0) >> 4, count = (role ? (n2 / 2) * B : n2 * B) >> 4, pred = planeBytes >> 4;
+        const int c2 = 2 * x265hipi_cujob_chroma_elems(ticket_format(ticket), n2);
+        const int planeBytes = (n2 + c2) * B;
+        const int first = (role ? n2 * B : 0) >> 4, count = (role ? c2 * B : n2 * B) >> 4, pred = planeBytes >> 4;
         // (bit 4 of the ticket: an inverse job — 1 024 levels behind the two blocks)
         const int extra = (ticket & 16) ? 128 : 0;
         for (int i = tid; i < 8 + 2 * count + extra; i += 256)
@@ -2053,21 +2064,22 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
     SlotIn* s = cs->in + slot;
     const x265hip_cujob& j = cs->shadow[slot];
     int sHi, sLo;
-    if (j.log2CUSize < 4 || j.log2CUSize > 6 || x265hipi_cujob_levels(&j, &sHi, &sLo) < 1 || !valid_depth((int)j.bitDepth))
-        return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: CU 2^%u, transform sizes 2^%u..2^%u, depth %u", j.log2CUSize, j.log2TrMin, j.log2TrMax, j.bitDepth);
+    if (j.log2CUSize < 4 || j.log2CUSize > 6 || x265hipi_cujob_levels(&j, &sHi, &sLo) < 1 || !valid_depth((int)j.bitDepth) || j.chroma > 3)
+        return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: CU 2^%u, transform sizes 2^%u..2^%u, depth %u, chroma format %u", j.log2CUSize, j.log2TrMin, j.log2TrMax,
+                         j.bitDepth, j.chroma);
     uint32_t run = cs->seq[slot].load(std::memory_order_relaxed) + 1;                       // a slot has one submitter at a time
     if (run >= 0xfffff0u) run = 1;
     cs->seq[slot].store(run, std::memory_order_relaxed);
     const bool inverseJob = j.coefMode == X265HIP_CUJOB_INVERSE;
     if (inverseJob && (j.log2CUSize != 5 || j.chroma || sHi != 5))
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: an inverse job is one 32x32 luma unit (CU 2^%u, chroma %u, transform 2^%d)", j.log2CUSize, j.chroma, sHi);
-    const uint32_t seq = (run << 8) | (j.log2CUSize - 4) | (j.chroma ? 4u : 0u) | (j.bitDepth > 8 ? 8u : 0u) | (inverseJob ? 16u : 0u);
+    const uint32_t seq = (run << 8) | (j.log2CUSize - 4) | (j.chroma ? 4u | ((j.chroma - 1) << 5) : 0u) | (j.bitDepth > 8 ? 8u : 0u) | (inverseJob ? 16u : 0u);
     *seqOut = seq;
     cs->jobs.fetch_add(1, std::memory_order_relaxed);
     {
         // SURVEY.md §8d, fused chain of one transform unit, as this job moves it: source + prediction in, levels + reconstructed residual out
         const uint64_t n2 = 1ull << (2 * j.log2CUSize), B = j.bitDepth > 8 ? 2 : 1;
-        cs->bytes.fetch_add((uint64_t)(sHi - sLo + 1) * (j.chroma ? n2 + n2 / 2 : n2) * (2 * B + 4), std::memory_order_relaxed);
+        cs->bytes.fetch_add((uint64_t)(sHi - sLo + 1) * (n2 + 2 * (uint64_t)x265hipi_cujob_chroma_elems(j.chroma, (int)n2)) * (2 * B + 4), std::memory_order_relaxed);
     }
     memcpy(&s->job, &j, sizeof(j));
     store_fence();                                                                           // header and pixels leave the core before the doorbell does
@@ -2090,6 +2102,11 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
     return X265HIP_OK;
 }
 
+uint32_t x265hip_cujob_formats(void)
+{
+    return 0xFu;                                                                             // 4:0:0, 4:2:0, 4:2:2, 4:4:4 (x265hip_cujob::chroma)
+}
+
 uint32_t x265hip_saojob_depths(void)
 {
     return (1u << 8) | (1u << 10) | (1u << 12);
@@ -2107,7 +2124,7 @@ int x265hip_cuserve_submit_sao(x265hip_cuserve* cs, int slot, const x265hip_saoj
     }
     const int bytes = ok ? x265hipi_saojob_pixel_bytes(job) : 0;
     // (the device fetches header + pixels in whole 512-byte steps, ticket_bytes: the last step has to end inside the slot's pixel block)
-    if (!ok || (128 + bytes + 511) / 512 * 512 > 128 + X265HIP_CUJOB_PIXEL_BYTES)
+    if (!ok || (128 + bytes + 511) / 512 * 512 > 128 + kSaoPixelBytes)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit_sao: depth %u, %u planes, luma %ux%u", job->bitDepth, job->planes, job->plane[0].w, job->plane[0].h);
     SlotIn* s = cs->in + slot;
     uint32_t run = cs->seq[slot].load(std::memory_order_relaxed) + 1;

@@ -192,6 +192,7 @@ PROTOTYPES = {
     "x265hip_cuserve_poke": (i32, [vp, i32]),
     "x265hip_cuserve_submit_sao": (i32, [vp, i32, vp, vp]),
     "x265hip_saojob_depths": (u32, []),
+    "x265hip_cujob_formats": (u32, []),
     "x265hip_cuserve_submit_intra": (i32, [vp, i32, vp, vp]),
     "x265hip_cuserve_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     "x265hip_device_time": (i32, [i32, vp, vp, vp]),
@@ -292,9 +293,9 @@ class CuJobUnit(C.Structure):
     _fields_ = [("ready", u32), ("numSig", u32), ("zeroDist", u64), ("codedDist", u64), ("readyInv", u32), ("fwdTicks", u32), ("codedEnergy", u32), ("reserved", u32 * 3)]
 
 
-CUJOB_MAX_UNITS = 60
-CUJOB_MAX_ELEMS = 2 * 6144
-CUJOB_PIXEL_BYTES = 2 * 6144 * 2
+CUJOB_MAX_UNITS = 100             # 4:2:2, 64x64, sizes 32 + 16
+CUJOB_MAX_ELEMS = 2 * 12288       # 4:4:4, 64x64, two levels
+CUJOB_PIXEL_BYTES = 2 * 12288 * 2
 
 
 class LaSearch(C.Structure):

@@ -13,8 +13,9 @@
 // (a mailbox slot in page-locked memory; x265_amd/csrc/cuserve.hip), and while the reference's own estimateResidualQT body runs on this
 // thread, Quant::transformNxN / ::invtransformNxN called for a residual block of that CU copy the device's result instead of computing it.
 // Same values either way (tests/test_cuserve.py pins the device against the oracle's restatement of those two functions, which is pinned
-// against the reference's); anything the job does not cover (transform skip, transquant bypass, scaling lists, noise reduction, RDOQ,
-// 4:2:2 / 4:4:4) runs the reference's functions as before.
+// against the reference's); anything the job does not cover (transform skip, transquant bypass, scaling lists, noise reduction)
+// runs the reference's functions as before.  Every chroma format is served (x265hip_cujob::chroma = the encoder's csp): a 4:2:2 chroma plane is N/2 x N with
+// the reference's two square sub-TUs per transform unit (search.cpp:3388-3393) as two rows of job units, a 4:4:4 one N x N with units of the luma size.
 //
 // Beside the transforms the job answers the distortions of the same blocks — cu[].sse_pp(source, prediction) and cu[].sse_pp(source, reconstruction)
 // of every unit (search.cpp:3269, :3295, and again at CU level :2872-2877) — and the time a thread spends waiting for the device goes into
@@ -46,6 +47,7 @@ std::atomic<int> g_lateJobs(0);
 int g_invJobs = X265_DEPTH == 8 ? 1 : 0;
 int g_rdoqJobs = 1;              // X265HIP_CUSERVE_RDOQ=0: CUs quantised by Quant::rdoQuant are not handed over (round 4's behaviour).  On: measured on the MI355X box at
                                  // BASELINE configs[2] / configs[3] (profiles/r05_v1_configs*_ab.txt): +2 % / +6 % fps, -3 % / -6 % CPU seconds
+int g_formats = 1;               // X265HIP_CUSERVE_FORMATS=0: CUs of 4:2:2 / 4:4:4 pictures are not handed over (what the binding did before their jobs existed)
 int g_slots = 64;                // X265HIP_CUSERVE_SLOTS: jobs that can be in flight (default: twice the CPUs this process may use, 16..64)
 bool g_verify = false;           // X265HIP_VERIFY=1: every served unit is recomputed by the reference's function and compared
 bool g_require = false;          // X265HIP=require: a device failure is fatal instead of falling back
@@ -59,7 +61,7 @@ std::atomic<bool> g_dead(false); // the device failed once: every later CU is co
 std::atomic<uint64_t> g_cycles[18][2], g_calls[18][2];
 __attribute__((tls_model("initial-exec"))) thread_local int t_inRqt = 0;
 
-struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped; };
+struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs; };
 Counters g_count[64];
 std::atomic<int> g_nextShard(0);
 __attribute__((tls_model("initial-exec"))) thread_local int t_shard = -1;
@@ -206,6 +208,13 @@ void report()
             fprintf(stderr, "x265hip: cuserve: %llu inverse jobs (luma 32x32 units of coefficient-mode CUs: dequant -> MFMA idct -> sse / psy energy behind Quant::rdoQuant's levels) "
                             "left when the levels were made, %llu never collected\n", (unsigned long long)ij, (unsigned long long)idr);
     }
+    {
+        uint64_t fj = 0;
+        for (int i = 0; i < 64; i++) fj += g_count[i].formatJobs;
+        if (fj)
+            fprintf(stderr, "x265hip: cuserve: %llu of the jobs were CUs of a 4:2:2 / 4:4:4 picture (4:2:2: the two CU-level N/2 x N chroma calls, sse_pp and sub_ps, "
+                            "stay on the host; every transform unit is served)\n", (unsigned long long)fj);
+    }
     if (dsb || dad)
         fprintf(stderr, "x265hip: cuserve: %llu sub_ps and %llu add_ps calls of those CUs put off because only the job's answers read their results (%llu + %llu run after all)\n",
                 (unsigned long long)dsb, (unsigned long long)dad, (unsigned long long)lsb, (unsigned long long)lad);
@@ -229,6 +238,7 @@ bool decide()
         if (getenv("X265HIP_CUSERVE_YIELD")) g_yieldAfter = atoi(getenv("X265HIP_CUSERVE_YIELD"));
         if (getenv("X265HIP_CUSERVE_RDOQ")) g_rdoqJobs = atoi(getenv("X265HIP_CUSERVE_RDOQ")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_INVERSE")) g_invJobs = atoi(getenv("X265HIP_CUSERVE_INVERSE")) ? 1 : 0;
+        if (getenv("X265HIP_CUSERVE_FORMATS")) g_formats = atoi(getenv("X265HIP_CUSERVE_FORMATS")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_TIMEOUT_MS") && atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) > 0) g_timeoutNs = atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) * 1000000ll;
         if (getenv("X265HIP_CUSERVE_SLOTS")) g_slots = atoi(getenv("X265HIP_CUSERVE_SLOTS"));
         else
@@ -336,14 +346,21 @@ int take_slot(Service** svc)
     return -1;
 }
 
+// the job's geometry: plane p of the CU is plane_w x plane_h samples, and a block of 2^lg samples in it belongs to the level of luma transform size level_of
+inline int hshift(const Job& j, int p) { return p ? x265hipi_cujob_hshift(j.hdr.chroma) : 0; }
+inline int vshift(const Job& j, int p) { return p ? x265hipi_cujob_vshift(j.hdr.chroma) : 0; }
+inline int plane_w(const Job& j, int p) { return (1 << j.log2CU) >> hshift(j, p); }
+inline int plane_h(const Job& j, int p) { return (1 << j.log2CU) >> vshift(j, p); }
+inline int level_of(const Job& j, int p, int lg) { return lg + hshift(j, p); }
+
 // unit of this thread's job a residual block belongs to, or -1
 inline int locate(const Job& j, const int16_t* residual, uint32_t resiStride, uint32_t log2TrSize, int ttype, int* elemOff)
 {
-    const int s = ttype ? (int)log2TrSize + 1 : (int)log2TrSize;
+    const int s = level_of(j, ttype, (int)log2TrSize);
     if (s > j.sHi || s < j.sLo || resiStride != j.resiStride[ttype]) return -1;
     const ptrdiff_t d = residual - j.resi[ttype];
-    const int N = (1 << j.log2CU) >> (ttype ? 1 : 0), n = 1 << log2TrSize;
-    if (d < 0 || d >= (ptrdiff_t)resiStride * N) return -1;
+    const int N = plane_w(j, ttype), n = 1 << log2TrSize;
+    if (d < 0 || d >= (ptrdiff_t)resiStride * plane_h(j, ttype)) return -1;
     const int y = (int)(d / resiStride), x = (int)(d % resiStride);
     if (x >= N || (x & (n - 1)) || (y & (n - 1))) return -1;
     *elemOff = x265hipi_cujob_elem_offset(j.job, j.sHi, s, ttype, x >> log2TrSize, y >> log2TrSize);
@@ -445,12 +462,16 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
     const bool codeChroma = csp != X265_CSP_I400 && se->m_frame->m_fencPic->m_picCsp != X265_CSP_I400;
     // RDOQ (presets slow / slower): the quantiser is Quant::rdoQuant and stays on the host (its decisions read the entropy coder's state); the job carries
     // the transforms in front of it — coefficient mode (X265HIP_CUSERVE_RDOQ=0 switches it off)
-    if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || (q.m_nr && q.m_nr->offset) || q.m_scalingList->m_bEnabled || (csp != X265_CSP_I420 && csp != X265_CSP_I400) ||
-        (csp == X265_CSP_I420) != codeChroma)
+    if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || (q.m_nr && q.m_nr->offset) || q.m_scalingList->m_bEnabled || csp < X265_CSP_I400 || csp > X265_CSP_I444 ||
+        (csp != X265_CSP_I400) != codeChroma)
+        return false;
+    // 4:2:2 / 4:4:4: only a library that says it takes such jobs gets them (an older one, or the emulated one of the tests, has no x265hip_cujob_formats: these
+    // CUs then stay on the host, as they do with X265HIP_CUSERVE_FORMATS=0)
+    if (csp > X265_CSP_I420 && (!g_formats || !x265hip_cujob_formats || !((x265hip_cujob_formats() >> csp) & 1)))
         return false;
     memset(&hdr, 0, sizeof(hdr));
     hdr.log2CUSize = log2CUSize; hdr.log2TrMax = depthRange[1]; hdr.log2TrMin = depthRange[0];
-    hdr.chroma = codeChroma; hdr.bitDepth = X265_DEPTH;
+    hdr.chroma = codeChroma ? csp : 0; hdr.bitDepth = X265_DEPTH;         // (X265_CSP_I420..I444 are the job's format numbers)
     hdr.quantOffset = cu.m_slice->m_sliceType == I_SLICE ? 171 : 85;
     hdr.signHide = cu.m_slice->m_pps->bSignHideEnabled;
     hdr.reserved = 0;
@@ -524,12 +545,12 @@ void inv_submit(Job& j, int u, int x, int y, const coeff_t* coeff)
     const int slot = take_slot(&svc);
     if (slot < 0)
         return;
-    const int N = 1 << j.log2CU, planeElems = j.hdr.chroma ? N * N + N * N / 2 : N * N;
+    const int N = 1 << j.log2CU, planeElems = N * N + 2 * x265hipi_cujob_chroma_elems(j.hdr.chroma, N * N);
     // the unit's source block, its prediction (out of this thread's copy of what the CU job was given), then its levels: one front-to-back copy into the mailbox
     alignas(64) unsigned char staged[2 * 1024 * sizeof(pixel) + 2048];
     pixel* dst = reinterpret_cast<pixel*>(staged);
-    pack_rows(dst, j.sent + (size_t)y * N + x, (uint32_t)N, 32);
-    pack_rows(dst, j.sent + planeElems + (size_t)y * N + x, (uint32_t)N, 32);
+    pack_rows(dst, j.sent + (size_t)y * N + x, (uint32_t)N, 32, 32);
+    pack_rows(dst, j.sent + planeElems + (size_t)y * N + x, (uint32_t)N, 32, 32);
     memcpy(dst, coeff, 2048);
     x265hip_cujob hdr = j.hdr;
     hdr.log2CUSize = 5; hdr.log2TrMax = 5; hdr.log2TrMin = 5; hdr.chroma = 0; hdr.coefMode = X265HIP_CUJOB_INVERSE; hdr.sourceDct = 0; hdr.reserved = 0;
@@ -572,10 +593,11 @@ bool submit(Search* se, Mode& mode, uint32_t log2CUSize, ShortYuv& resiYuv, cons
     // packed in this thread's own memory first (what encodeResAndCalcRdInterCU compares a job submitted ahead with), then one front-to-back copy into the
     // mailbox — device memory behind a write-combining mapping likes that better than 16- and 32-byte rows anyway
     pixel* dst = j.sent;
-    pack_rows(dst, fenc->m_buf[0], fenc->m_size, N);
-    if (codeChroma) { pack_rows(dst, fenc->m_buf[1], fenc->m_csize, N / 2); pack_rows(dst, fenc->m_buf[2], fenc->m_csize, N / 2); }
-    pack_rows(dst, pred->m_buf[0], pred->m_size, N);
-    if (codeChroma) { pack_rows(dst, pred->m_buf[1], pred->m_csize, N / 2); pack_rows(dst, pred->m_buf[2], pred->m_csize, N / 2); }
+    const int cw = N >> x265hipi_cujob_hshift(hdr.chroma), ch = N >> x265hipi_cujob_vshift(hdr.chroma);
+    pack_rows(dst, fenc->m_buf[0], fenc->m_size, N, N);
+    if (codeChroma) { pack_rows(dst, fenc->m_buf[1], fenc->m_csize, cw, ch); pack_rows(dst, fenc->m_buf[2], fenc->m_csize, cw, ch); }
+    pack_rows(dst, pred->m_buf[0], pred->m_size, N, N);
+    if (codeChroma) { pack_rows(dst, pred->m_buf[1], pred->m_csize, cw, ch); pack_rows(dst, pred->m_buf[2], pred->m_csize, cw, ch); }
     memcpy(mem.pixels, j.sent, (size_t)(dst - j.sent) * sizeof(pixel));
     if (x265hip_cuserve_submit(svc->cs, slot, &j.seq))
     {
@@ -609,6 +631,7 @@ bool submit(Search* se, Mode& mode, uint32_t log2CUSize, ShortYuv& resiYuv, cons
     j.job = mem.job; j.units = mem.units; j.levels = mem.levels; j.resiOut = mem.resi;
     j.active = true;
     counters().jobs.fetch_add(1, std::memory_order_relaxed);
+    if (hdr.chroma > 1) counters().formatJobs.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -624,7 +647,9 @@ void end_job()
     j.pendSub[0].pending = j.pendSub[1].pending = j.pendSub[2].pending = false;
     if (done)
     {
-        const int last = x265hipi_cujob_unit_index(j.job, j.sHi, j.sLo, j.resi[1] ? 2 : 0, (1 << (j.log2CU - j.sLo)) - 1, (1 << (j.log2CU - j.sLo)) - 1);
+        // (the last unit of the smallest level: the bottom right one of Cr — a 4:2:2 plane has twice as many rows of units as columns — or of Y)
+        const int perRow = 1 << (j.log2CU - j.sLo), rows = j.resi[1] ? perRow * x265hipi_cujob_chroma_units(j.hdr.chroma) : perRow;
+        const int last = x265hipi_cujob_unit_index(j.job, j.sHi, j.sLo, j.resi[1] ? 2 : 0, perRow - 1, rows - 1);
         for (int u = 0; u <= last && done; u++)
             done = wait_word(j, &j.units[u].readyInv, 5);
     }
@@ -642,13 +667,13 @@ inline bool where_in_source(const Job& j, const pixel* src, intptr_t stride, int
     {
         if (!j.fenc[p] || (uint32_t)stride != j.fencStride[p]) continue;
         const ptrdiff_t d = src - j.fenc[p];
-        const int N = (1 << j.log2CU) >> (p ? 1 : 0);
-        if (d < 0 || d >= (ptrdiff_t)stride * N) continue;
+        const int W = plane_w(j, p), H = plane_h(j, p);
+        if (d < 0 || d >= (ptrdiff_t)stride * H) continue;
         const int y = (int)(d / stride), x = (int)(d % stride);
-        if (x >= N || (x & (n - 1)) || (y & (n - 1)) || x + n > N || y + n > N) return false;
+        if (x >= W || (x & (n - 1)) || (y & (n - 1)) || x + n > W || y + n > H) return false;
         int lg = 0;
         while ((1 << lg) < n) lg++;
-        w.plane = p; w.x = x; w.y = y; w.n = n; w.s = p ? lg + 1 : lg;
+        w.plane = p; w.x = x; w.y = y; w.n = n; w.s = level_of(j, p, lg);
         return true;
     }
     return false;
@@ -665,7 +690,7 @@ inline bool job_sse(Job& j, const pixel* a, intptr_t sa, const pixel* b, intptr_
         // the unit itself, or — a block above the largest transform size (a 64x64 CU) — the sum over the units it is made of (sse is additive)
         const int s = w.s > j.sHi ? j.sHi : w.s;
         if (s < j.sLo) return false;
-        const int k = 1 << (w.s - s), sh = w.plane ? s - 1 : s;
+        const int k = 1 << (w.s - s), sh = s - hshift(j, w.plane);
         uint64_t sum = 0;
         for (int ty = 0; ty < k; ty++)
             for (int tx = 0; tx < k; tx++)
@@ -682,7 +707,7 @@ inline bool job_sse(Job& j, const pixel* a, intptr_t sa, const pixel* b, intptr_
     const Yuv& rq = j.search->m_rqt[w.s - 2].reconQtYuv;
     const uint32_t rs = w.plane ? rq.m_csize : rq.m_size;
     if ((uint32_t)sb != rs || b != rq.m_buf[w.plane] + (size_t)w.y * rs + w.x) return false;
-    const int sh = w.plane ? w.s - 1 : w.s;
+    const int sh = w.s - hshift(j, w.plane);
     const int u = x265hipi_cujob_unit_index(j.job, j.sHi, w.s, w.plane, w.x >> sh, w.y >> sh);
     if (!j.invServed[u] || !wait_word(j, &j.units[u].readyInv, 4)) { flush_add(j, u); return false; }
     out = j.units[u].codedDist;
@@ -699,11 +724,11 @@ template <typename F> inline bool final_sum(Job& j, const pixel* a, intptr_t sa,
     // "one transform size in the job" must also mean "one transform size in the TREE": x265hipi_cujob_levels clamps the job's smallest size to 16, the tree
     // may go below it (--max-tu-size 16 --tu-inter-depth 3: depthRange [3, 4]) and a unit split further has neither the job's coded nor its zero answer
     if (g_serveDist < 2 || j.inTree || j.sHi != j.sLo || (int)j.job->log2TrMin < j.sLo || !where_in_source(j, a, sa, n, w) || w.x || w.y) return false;
-    const int N = (1 << j.log2CU) >> (w.plane ? 1 : 0);
-    if (n != N) return false;
+    // (a 4:2:2 chroma plane is not square: the CU-level questions about it do not come through these slots, and a transform unit's cbf there speaks for two units)
+    if (n != plane_w(j, w.plane) || n != plane_h(j, w.plane)) return false;
     const Yuv& ry = j.mode->reconYuv;
     if ((uint32_t)sb != (w.plane ? ry.m_csize : ry.m_size) || b != ry.m_buf[w.plane]) return false;
-    const int s = j.sHi, k = 1 << (j.log2CU - s), sh = w.plane ? s - 1 : s, tuDepth = (int)j.log2CU - s;
+    const int s = j.sHi, k = 1 << (j.log2CU - s), tuDepth = (int)j.log2CU - s;
     const CUData& cu = j.mode->cu;
     int64_t sum = 0;
     for (int ty = 0; ty < k; ty++)
@@ -716,7 +741,6 @@ template <typename F> inline bool final_sum(Job& j, const pixel* a, intptr_t sa,
             if (!unit_value(u, cbf, v)) return false;
             sum += v;
         }
-    (void)sh;
     out = sum;
     return true;
 }
@@ -819,7 +843,7 @@ template <int CU, int N> int psy_slot(const pixel* a, intptr_t sa, const pixel* 
         const uint32_t rs = w.plane ? rq.m_csize : rq.m_size;
         if ((uint32_t)sb == rs && b == rq.m_buf[w.plane] + (size_t)w.y * rs + w.x)
         {
-            const int sh = w.plane ? w.s - 1 : w.s;
+            const int sh = w.s - hshift(j, w.plane);
             const int u = x265hipi_cujob_unit_index(j.job, j.sHi, w.s, w.plane, w.x >> sh, w.y >> sh);
             if (j.invServed[u] && wait_word(j, &j.units[u].readyInv, 4))
             {
@@ -836,7 +860,7 @@ template <int CU, int N> int psy_slot(const pixel* a, intptr_t sa, const pixel* 
         const int s = w.s > j.sHi ? j.sHi : w.s;
         if (s >= j.sLo)
         {
-            const int k = 1 << (w.s - s), sh = w.plane ? s - 1 : s;
+            const int k = 1 << (w.s - s), sh = s - hshift(j, w.plane);
             bool all = true;
             int64_t sum = 0;
             for (int ty = 0; ty < k && all; ty++)
@@ -871,8 +895,9 @@ template <int CU, int N, bool CHROMA> void sub_ps_slot(int16_t* dst, intptr_t ds
 {
     Job& j = t_job;
     const pixel_sub_ps_t fn = CHROMA ? g_prev.chroma[X265_CSP_I420].cu[CU].sub_ps : g_prev.cu[CU].sub_ps;
+    // (4:4:4: chroma[X265_CSP_I444].cu[] holds the luma functions, primitives.cpp:124-134, so the chroma planes' calls arrive in the luma slot)
     if (j.active && !j.inTree && !j.treeMine && t_inEncodeRes && g_serveDist >= 3 && !g_verify && (N << (CHROMA ? 1 : 0)) == (1 << j.log2CU))
-        for (int p = CHROMA ? 1 : 0; p < (CHROMA ? 3 : 1); p++)
+        for (int p = CHROMA ? 1 : 0; p < (CHROMA || j.hdr.chroma == X265_CSP_I444 ? 3 : 1); p++)
             if (dst == j.resi[p] && (uint32_t)ds == j.resiStride[p] && a == j.fenc[p] && (uint32_t)sa == j.fencStride[p] && b == j.pred[p] && (uint32_t)sb == j.predStride[p])
             {
                 j.pendSub[p] = Job::PendSub{ true, dst, ds, a, b, sa, sb, fn };
@@ -898,13 +923,13 @@ template <int CU, int N, int AL> void add_ps_slot(pixel* dst, intptr_t ds, const
         {
             if (!j.pred[p] || (uint32_t)sa != j.predStride[p]) continue;
             const ptrdiff_t d = a - j.pred[p];
-            const int W = (1 << j.log2CU) >> (p ? 1 : 0);
-            if (d < 0 || d >= (ptrdiff_t)sa * W) continue;
+            const int W = plane_w(j, p);
+            if (d < 0 || d >= (ptrdiff_t)sa * plane_h(j, p)) continue;
             const int y = (int)(d / sa), x = (int)(d % sa);
             if (x >= W || (x & (N - 1)) || (y & (N - 1))) break;
             int lg = 0;
             while ((1 << lg) < N) lg++;
-            const int s = p ? lg + 1 : lg;
+            const int s = level_of(j, p, lg);
             if (s > j.sHi || s < j.sLo) break;
             const Yuv& rq = j.search->m_rqt[s - 2].reconQtYuv;
             const ShortYuv& rs = j.search->m_rqt[s - 2].resiQtYuv;
@@ -1114,9 +1139,9 @@ bool adopt(Search* se, Mode& mode, const CUGeom& cuGeom)
         for (int p = 0; p < (j.pred[1] ? 3 : 1); p++)
         {
             const Yuv& y = half ? pred : fenc;
-            const int n = p ? N / 2 : N;
+            const int n = p ? N >> x265hipi_cujob_hshift(j.hdr.chroma) : N, rows = p ? N >> x265hipi_cujob_vshift(j.hdr.chroma) : N;
             const uint32_t st = p ? y.m_csize : y.m_size;
-            for (int r = 0; r < n; r++, sent += n)
+            for (int r = 0; r < rows; r++, sent += n)
                 if (memcmp(y.m_buf[p] + (size_t)r * st, sent, sizeof(pixel) * n))
                     return false;
         }
@@ -1234,8 +1259,15 @@ uint32_t Quant::transformNxN(const CUData& cu, const pixel* fenc, uint32_t fencS
                 const int x = (int)(d % resiStride), y = (int)(d / resiStride), n = 1 << log2TrSize;
                 psy_ahead(j, u, (int)ttype, x, y, n);
                 if (ttype == TEXT_LUMA && j.resi[1] && n >= 16)
-                    for (int p = 1; p <= 2 && __atomic_load_n(&j.units[u].ready, __ATOMIC_ACQUIRE) != j.seq; p++)
-                        psy_ahead(j, x265hipi_cujob_unit_index(j.job, j.sHi, (int)log2TrSize, p, x >> log2TrSize, y >> log2TrSize), p, x >> 1, y >> 1, n >> 1);
+                {
+                    // (chroma units of n >> hs samples; 4:2:2 has two of them per plane, one below the other)
+                    const int hs = hshift(j, 1), vs = vshift(j, 1), nc = n >> hs, per = x265hipi_cujob_chroma_units(j.hdr.chroma);
+                    for (int k = 0; k < 2 * per && __atomic_load_n(&j.units[u].ready, __ATOMIC_ACQUIRE) != j.seq; k++)
+                    {
+                        const int p = 1 + k / per, sub = k % per;
+                        psy_ahead(j, x265hipi_cujob_unit_index(j.job, j.sHi, (int)log2TrSize, p, x >> log2TrSize, (int)(y >> log2TrSize) * per + sub), p, x >> hs, (y >> vs) + sub * nc, nc);
+                    }
+                }
             }
             if (j.hdr.coefMode)
             {
@@ -1379,13 +1411,13 @@ void Quant::invtransformNxN(const CUData& cu, int16_t* residual, uint32_t resiSt
     {
         // which unit?  the one of this size and plane whose levels these are: equal levels have equal inverse transforms, so the comparison — not
         // any bookkeeping — is what makes the copy exact.  The tree asks for a unit's inverse right after its forward transform: look there first.
-        const int s = ttype ? (int)log2TrSize + 1 : (int)log2TrSize;
+        const int s = level_of(j, (int)ttype, (int)log2TrSize);
         if (s <= j.sHi && s >= j.sLo && (ttype == TEXT_LUMA || j.resi[ttype]))
         {
             const uint64_t t0 = g_time ? __builtin_ia32_rdtsc() : 0;
-            const int per = 1 << (j.log2CU - s), n = 1 << log2TrSize, n2 = n * n;
+            const int per = 1 << (j.log2CU - s), n = 1 << log2TrSize, n2 = n * n, count = per * per * (ttype ? x265hipi_cujob_chroma_units(j.hdr.chroma) : 1);
             const int first = x265hipi_cujob_unit_index(j.job, j.sHi, s, (int)ttype, 0, 0), eo0 = x265hipi_cujob_elem_offset(j.job, j.sHi, s, (int)ttype, 0, 0);
-            for (int t = 0; t < per * per; t++)
+            for (int t = 0; t < count; t++)
             {
                 const x265hip_cujob_unit& un = j.units[first + t];
                 if (__atomic_load_n(&un.ready, __ATOMIC_ACQUIRE) != j.seq || un.numSig != numSig || memcmp(coeff, j.levels + eo0 + t * n2, sizeof(coeff_t) * n2))

@@ -34,6 +34,9 @@
 #include "x265hip.h"
 #include "x265_hip_debug.h"
 
+// not in every library these seams are linked against (the emulated one of the tests, an older libx265hip): absent = 4:2:0 and 4:0:0 jobs only
+extern "C" uint32_t x265hip_cujob_formats(void) __attribute__((weak));
+
 namespace X265_NS {
 
 
@@ -90,11 +93,12 @@ void touch_shard();                          // gives the calling thread its cou
 bool service();                              // opens the services on first use; false: no device
 int take_slot(Service** svc);                // a free slot for this thread's next job, or -1
 inline void give_slot(Service* sv, int s) { sv->busy[s >> 6].fetch_and(~(1ull << (s & 63)), std::memory_order_release); }
-template <typename T> inline void pack_rows(T*& dst, const T* src, uint32_t stride, int n)
+template <typename T> inline void pack_rows(T*& dst, const T* src, uint32_t stride, int n, int rows)
 {
-    if ((int)stride == n) { memcpy(dst, src, sizeof(T) * n * n); dst += n * n; return; }
-    for (int y = 0; y < n; y++, dst += n) memcpy(dst, src + (size_t)y * stride, sizeof(T) * n);
+    if ((int)stride == n) { memcpy(dst, src, sizeof(T) * n * rows); dst += n * rows; return; }
+    for (int y = 0; y < rows; y++, dst += n) memcpy(dst, src + (size_t)y * stride, sizeof(T) * n);
 }
+template <typename T> inline void pack_rows(T*& dst, const T* src, uint32_t stride, int n) { pack_rows(dst, src, stride, n, n); }
 // X265HIP_DEBUG_CUTIME: cycles of one call into the table of report_time()
 struct Timed
 {
