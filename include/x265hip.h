@@ -835,8 +835,9 @@ int x265hip_call_frame_init_lowres(int depth, const void* src, int64_t srcStride
  * x265_hip_cuserve.cpp) keeps the entropy coder and every decision.  Jobs travel through mailbox SLOTS in page-locked host memory
  * that the device reads and writes directly: the caller fills the slot's job header and pixel block, submits, and polls the
  * per-unit `ready` / `readyInv` words (each unit's forward half — numSig and levels — is published as soon as it is done, luma first;
- * its inverse half follows).  Flat quantiser only (no scaling lists), no
- * transform skip, no transquant bypass, no noise reduction, no RDOQ: the caller does not submit such CUs.
+ * its inverse half follows).  Flat quantiser, or the quantiser and dequantiser matrices of a scaling list from a table set registered on the
+ * service (x265hip_cujob::scaling, x265hip_cujob_scaling_add); no transform skip, no transquant bypass, no noise reduction: the caller does
+ * not submit such CUs.  RDOQ: coefficient mode (x265hip_cujob::coefMode).
  *
  * Chroma format of a job (x265hip_cujob::chroma, the values of X265_CSP_I400..I444) and its chroma shifts hs / vs: 0 no chroma, 1 4:2:0 (1 / 1),
  * 2 4:2:2 (1 / 0), 3 4:4:4 (0 / 0); x265hip_cujob_formats() tells which of them the library accepts.
@@ -865,6 +866,11 @@ typedef struct x265hip_cujob
                                    * so is everything else the unit will get (the luma units' source transform with sourceDct: it may arrive before or after) */
     uint32_t sourceDct;           /* with coefMode: 1 = a LUMA unit's `resi` block receives cu[].dct of the unit's SOURCE pixels — m_fencDctCoeff, which psy-rdoq
                                    * compares the levels' reconstruction against (quant.cpp:436-442) */
+    uint32_t scaling;             /* 0: flat quantiser, quantScale[] / dequantScale[] above.  Non-zero: the id of a table set registered on the service
+                                   * (x265hip_cujob_scaling_add): every unit is quantised with m_quantCoef[size][3 + plane][rem][] (quant.cpp:460-476) and
+                                   * dequantised by dequant_scaling with m_dequantCoef[size][3 + plane][rem][] (quant.cpp:559-564, dct.cpp:636-662); the two
+                                   * scale arrays are ignored.  A coefficient-mode job may carry an id (unused: the host quantises); an inverse job
+                                   * dequantises with the set's 32x32 luma table */
 } x265hip_cujob;
 /* coefMode == X265HIP_CUJOB_INVERSE: the INVERSE half alone, for levels the host has made (Quant::rdoQuant): Quant::invtransformNxN (quant.cpp:543-603:
  * dequant_normal -> cu[].idct) of ONE 32x32 luma unit and the measurements Search::estimateResidualQT takes behind it.  log2CUSize = log2TrMax = 5, chroma = 0;
@@ -930,6 +936,13 @@ X265HIP_HD static inline int x265hipi_cujob_elem_offset(const x265hip_cujob* j, 
 }
 /* the chroma formats this library's CU jobs accept: bit f set for x265hip_cujob::chroma == f (0xF here).  Needs no device. */
 uint32_t x265hip_cujob_formats(void);
+/* what else this library's CU jobs can do: bit 0 = table sets of scaling lists (x265hip_cujob::scaling).  Needs no device. */
+uint32_t x265hip_cujob_features(void);
+/* A table set = the quantiser and dequantiser matrices of the inter lists a job uses, packed [size 8, 16, 32][plane Y, Cb, Cr][rem 0..5][n * n] (rows
+ * contiguous: ScalingList::m_quantCoef / m_dequantCoef [1..3][3..5][0..5] as the encoder holds them, scalinglist.cpp:342-415).  quant_c multiplies in int:
+ * the caller registers only lists whose entries are all >= 8 (quantCoef <= 52 428), below that the reference's own arithmetic overflows. */
+#define X265HIP_CUJOB_SCALING_ENTRIES ((64 + 256 + 1024) * 3 * 6)
+#define X265HIP_CUJOB_SCALING_SETS    8
 typedef struct x265hip_cuserve x265hip_cuserve;
 /* mode 0: a resident server kernel per slot group polls the slots' doorbells (started on demand, ends by itself after `idle
  * microseconds` without work so that nothing in the process ever waits on it for long); mode 1: one launch per job on the slot's own
@@ -951,6 +964,13 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seq);
  * way onto the chip; X265HIP_EHIP (negative): the device reported a failure, the caller gives up the job and computes on the host */
 int x265hip_cuserve_poke(x265hip_cuserve* cs, int slot);
 int x265hip_cuserve_stats(x265hip_cuserve* cs, uint64_t* jobs, uint64_t* serverStarts, uint64_t* deviceNs);
+/* (named x265hip_cujob_*, like x265hip_cujob_formats: the x265hip_cuserve_* entry points are the ones EVERY implementation of the job ABI has, the CPU
+ * emulation of the tests included; this one and x265hip_cujob_features are optional and looked up through weak references)
+ * registers a table set (X265HIP_CUJOB_SCALING_ENTRIES int32 each) on the service: both arrays are in device memory when the call returns, and *id (1 ..
+ * X265HIP_CUJOB_SCALING_SETS) is what x265hip_cujob::scaling of a later job names.  A set is never modified or freed before x265hip_cuserve_close.  One set
+ * more than X265HIP_CUJOB_SCALING_SETS: X265HIP_EINVAL, the service goes on serving.  A resident server is made to leave and start again around the copy
+ * (waiters see x265hip_cuserve_poke == 1 meanwhile), so that the tables are first read by a kernel launched after they were written. */
+int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id);
 
 /* ---- SAO statistics of one CTU as a job of the same service (round 5) ---------------------------------------------------------------------
  * SAO::calcSaoStatsCTU (reference source/encoder/sao.cpp:735-917; called per plane from rdoSaoUnitCu :1293-1305) measures, for the deblocked CTU, the

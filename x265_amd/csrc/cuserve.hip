@@ -135,7 +135,8 @@ static_assert(sizeof(x265hip_cujob) <= 128, "job header");
 
 // ticket = what the host rings and the units' ready words take: bits 31..8 a running number (never 0, never 0xffffff), bits 7..0 what the device
 // needs to know before it has read anything: log2CUSize - 4 (bits 1..0), chroma (bit 2), 16-bit samples (bit 3), an inverse job's levels block (bit 4),
-// the chroma format beyond 4:2:0 (bits 6..5: x265hip_cujob::chroma - 1 of a job with chroma, so 4:2:0 and 4:0:0 tickets are what they always were)
+// the chroma format beyond 4:2:0 (bits 6..5: x265hip_cujob::chroma - 1 of a job with chroma, so 4:2:0 and 4:0:0 tickets are what they always were), a table
+// set to quantise with (bit 7: flat jobs' tickets are what they always were)
 // bits 1..0 == 3: an SAO statistics job (x265hip_saojob): bits 7..2 = the job's size, header included, in 512-byte steps
 __host__ __device__ inline uint32_t ticket_format(uint32_t t) { return (t & 4) ? 1 + ((t >> 5) & 3) : 0; }      // x265hip_cujob::chroma of a CU job's ticket
 __host__ __device__ inline uint32_t ticket_bytes(uint32_t t)
@@ -149,9 +150,32 @@ __host__ __device__ inline uint32_t ticket_bytes(uint32_t t)
 constexpr int kSaoPixelBytes = 2 * 6144 * 2;
 static_assert(kSaoPixelBytes <= X265HIP_CUJOB_PIXEL_BYTES && (128 + kSaoPixelBytes) / 512 <= 63, "SAO statistics job: pixel block, ticket size field");
 
-struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal; };
+// qTab / dqTab: the unit's (size, plane, rem) matrices of the job's table set (x265hip_cujob::scaling), n * n int32 each, rows contiguous; null: the flat quantiser.
+// per: the plane's qpParam.per, which dequant_scaling takes apart from the matrix
+struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal, per; const int32_t* qTab; const int32_t* dqTab; };
 
-__device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int plane, int log2n)
+// A table set in device memory: X265HIP_CUJOB_SCALING_ENTRIES quantiser entries, then as many dequantiser entries; [size 8, 16, 32][plane][rem][n * n]
+constexpr int kSetInts = 2 * X265HIP_CUJOB_SCALING_ENTRIES;
+__host__ __device__ inline int scaling_offset(int log2n, int plane, int rem)
+{
+    const int before = log2n == 3 ? 0 : log2n == 4 ? 64 * 18 : (64 + 256) * 18;
+    return before + ((plane * 6 + rem) << (2 * log2n));
+}
+
+// dequant_scaling_c (dct.cpp:636-662) of one level: shift = the flat dequantiser's shift + 4
+__device__ __forceinline__ int dequant_table(int lv, int dqc, int per, int shift)
+{
+    if (shift > per)
+        return clip3i(-32768, 32767, (lv * dqc + (1 << (shift - per - 1))) >> (shift - per));
+    return clip3i(-32768, 32767, clip3i(-32768, 32767, lv * dqc) << (per - shift));
+}
+__device__ __forceinline__ void load_table4(const int32_t* p, int* v)
+{
+    const int4 q = *reinterpret_cast<const int4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+
+__device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int plane, int log2n, const int32_t* sets)
 {
     // quant.cpp:408 transformShift = MAX_TR_DYNAMIC_RANGE(15) - depth - log2TrSize; :461 qbits = QUANT_SHIFT(14) + per + transformShift;
     // :466 add = offset << (qbits - 9); :556 shift = QUANT_IQUANT_SHIFT(20) - QUANT_SHIFT - transformShift; :567 scale = invQuantScales[rem] << per
@@ -166,13 +190,23 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
     p.s1f = log2n - 1 + (depth - 8); p.s2f = log2n + 6;
     p.s1i = 7; p.s2i = 12 - (depth - 8);
     p.maxVal = (1 << depth) - 1;
+    p.per = j.qpPer[plane];
+    p.qTab = p.dqTab = nullptr;
+    if (j.scaling && sets)
+    {
+        // (x265hip_cuserve_submit has looked at the id and at rem: the offsets stay inside the set)
+        p.qTab = sets + (size_t)(j.scaling - 1) * kSetInts + scaling_offset(log2n, plane, j.qpRem[plane]);
+        p.dqTab = p.qTab + X265HIP_CUJOB_SCALING_ENTRIES;
+    }
     return p;
 }
 
 // One tile: units u0 .. u0 + G - 1 (G = (32 / N)^2, raster order, `count` of them exist) of size N x N of one plane.
 //   src / prd: the plane's source and prediction in LDS, `pw` elements per row; the plane has pw / N units per row (as many rows of them as the caller counts:
 //   pw / N, twice that for a 4:2:2 chroma plane)
-template <typename P, int N>
+// SC: the units are quantised and dequantised with the matrices qp.qTab / qp.dqTab (a lane's 16 coefficients are 16 contiguous int32 of the matrix: four
+// 16-byte loads, issued ahead of the stage in front of the one that needs them); the flat instantiation is the code it was
+template <typename P, int N, bool SC>
 __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64], const P* src, const P* prd, int pw, int u0, int count, const PlaneParams qp,
                                            bool signHide, x265hip_cujob_unit* units, int unitBase, int16_t* levels, int16_t* resi, int elemBase, uint32_t seq, uint64_t t0, bool stamps,
                                            int coef)
@@ -194,6 +228,12 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
     // coef (x265hip_cujob::coefMode): bit 0 the residual's transform coefficients go out, bit 1 the source block's; bit 2: the two parts are separate work
     // items on different waves (the residual part releases `ready`, the source part `readyInv`)
     const bool srcOnly = (coef & 3) == 2;
+    [[maybe_unused]] int qs[16], dqs[16];
+    if constexpr (SC)
+    {
+#pragma unroll
+        for (int k = 0; k < 4; k++) load_table4(qp.qTab + ((lane * 16) % (N * N)) + 4 * k, qs + 4 * k);
+    }
     // ---- residual = source - prediction (two runs of 8 per lane; kept in registers for the distortions)
     int fv[16], pv[16];
 #pragma unroll
@@ -284,7 +324,9 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
 #pragma unroll
         for (int i = 0; i < 8; i++)
         {
-            const int tmp = iabs(cf[i]) * qp.quantScale;
+            int scale = qp.quantScale;
+            if constexpr (SC) scale = qs[8 * half + i];
+            const int tmp = iabs(cf[i]) * scale;
             const int l = (tmp + qp.add) >> qp.qBits;
             du[i] = (tmp - (l << qp.qBits)) >> qBits8;
             cnt += l != 0;
@@ -292,6 +334,11 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
         }
         store4(t.b + e, lv); store4(t.b + e + 4, lv + 4);
         store4(t.c + e, du); store4(t.c + e + 4, du + 4);
+    }
+    if constexpr (SC)
+    {
+#pragma unroll
+        for (int k = 0; k < 4; k++) load_table4(qp.dqTab + ((lane * 16) % (N * N)) + 4 * k, dqs + 4 * k);
     }
     int numSig = group_sum(cnt, LPT);                       // of the unit this lane belongs to (lanes g * LPT .. g * LPT + LPT - 1)
     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -388,7 +435,11 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
             int lv[8], dq[8];
             load4(t.b + e, lv); load4(t.b + e + 4, lv + 4);
 #pragma unroll
-            for (int i = 0; i < 8; i++) dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+            for (int i = 0; i < 8; i++)
+            {
+                if constexpr (SC) dq[i] = dequant_table(lv[i], dqs[8 * half + i], qp.per, qp.dqShift + 4);
+                else dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+            }
             if (okL)
                 *reinterpret_cast<uint4*>(levels + elemBase + (u0 + gL) * N * N + (e % (N * N))) = *reinterpret_cast<const uint4*>(t.b + e);
             store4(t.a + e, dq); store4(t.a + e + 4, dq + 4);
@@ -669,7 +720,7 @@ __device__ __forceinline__ void team_inverse32(TileLds& t, TeamLds& tm, const P*
 }
 
 // unit `u` (raster order; `pw` elements per row of the plane in LDS) of a plane whose transform size is 32: tile_chain<P, 32>'s work for one unit
-template <typename P>
+template <typename P, bool SC>
 __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* src, const P* prd, int pw, int u, const PlaneParams qp, bool signHide,
                                              x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef)
 {
@@ -682,6 +733,9 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
     const bool srcOnly = (coef & 3) == 2;
     // ---- residual: four consecutive samples of a row per thread, kept in registers for the distortions
     const int e = tid * 4;
+    // (SC: the thread's four entries of the quantiser matrix, one 16-byte load that the forward transform hides)
+    [[maybe_unused]] int qs[4], dqs[4];
+    if constexpr (SC) load_table4(qp.qTab + e, qs);
     int fv[4], pv[4];
     {
         const int off = (uy * 32 + (e >> 5)) * pw + ux * 32 + (e & 31);
@@ -743,7 +797,9 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
 #pragma unroll
         for (int i = 0; i < 4; i++)
         {
-            const int tmp = iabs(cf[i]) * qp.quantScale;
+            int scale = qp.quantScale;
+            if constexpr (SC) scale = qs[i];
+            const int tmp = iabs(cf[i]) * scale;
             const int l = (tmp + qp.add) >> qp.qBits;
             du[i] = (tmp - (l << qp.qBits)) >> qBits8;
             cnt += l != 0;
@@ -752,6 +808,7 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
         store4(t.b + e, lv);
         store4(t.c + e, du);
         team_part(tm.part, tid, cnt);
+        if constexpr (SC) load_table4(qp.dqTab + e, dqs);
     }
     team_barrier();
     XH_STAMP(2);
@@ -848,7 +905,11 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
         const int dqAdd = 1 << (qp.dqShift - 1);
         load4(t.b + e, lv);
 #pragma unroll
-        for (int i = 0; i < 4; i++) dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+        for (int i = 0; i < 4; i++)
+        {
+            if constexpr (SC) dq[i] = dequant_table(lv[i], dqs[i], qp.per, qp.dqShift + 4);
+            else dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+        }
         store4(t.a + e, dq);
         if (wv == 0)
         {
@@ -960,7 +1021,7 @@ __device__ __forceinline__ unsigned long long solo_total(uint32_t v)
            (uint32_t)__builtin_amdgcn_readlane((int)r, 32) + (uint32_t)__builtin_amdgcn_readlane((int)r, 48);
 }
 
-template <typename P>
+template <typename P, bool SC>
 __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)[64], const P* src, const P* prd, const PlaneParams qp, bool signHide,
                                              x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef)
 {
@@ -969,6 +1030,8 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
     const int lane = threadIdx.x & 63, e = lane * 4;
     const TeamOperand& oF = op[0][lane];
     const TeamOperand& oI = op[1][lane];
+    [[maybe_unused]] int qs[4], dqs[4];
+    if constexpr (SC) load_table4(qp.qTab + e, qs);
     int fv[4], pv[4];
     {
         load4(src + e, fv);
@@ -1011,7 +1074,9 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
 #pragma unroll
         for (int i = 0; i < 4; i++)
         {
-            const int tmp = iabs(cf[i]) * qp.quantScale;
+            int scale = qp.quantScale;
+            if constexpr (SC) scale = qs[i];
+            const int tmp = iabs(cf[i]) * scale;
             const int l = (tmp + qp.add) >> qp.qBits;
             du[i] = (tmp - (l << qp.qBits)) >> qBits8;
             cnt += l != 0;
@@ -1019,6 +1084,7 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
         }
         store4(t.b + e, lv);
         store4(t.c + e, du);
+        if constexpr (SC) load_table4(qp.dqTab + e, dqs);
     }
     int numSig = wave_sum((int)cnt);
     XH_STAMP(2);
@@ -1108,7 +1174,11 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
         const int dqAdd = 1 << (qp.dqShift - 1);
         load4(t.b + e, lv);
 #pragma unroll
-        for (int i = 0; i < 4; i++) dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+        for (int i = 0; i < 4; i++)
+        {
+            if constexpr (SC) dq[i] = dequant_table(lv[i], dqs[i], qp.per, qp.dqShift + 4);
+            else dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+        }
         *reinterpret_cast<uint2*>(levels + e) = *reinterpret_cast<const uint2*>(t.b + e);
         store4(t.a + e, dq);
     }
@@ -1175,8 +1245,8 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
 // An INVERSE job (x265hip_cujob::coefMode == X265HIP_CUJOB_INVERSE): one 32x32 luma unit whose levels the host has made (Quant::rdoQuant) — dequant_normal ->
 // cu[].idct -> reconstructed residual, sse_pp and psy energy of the reconstruction, i.e. Quant::invtransformNxN (quant.cpp:543-603) and the two measurements
 // Search::estimateResidualQT takes behind it (search.cpp:3290-3300).  The levels follow the source and prediction blocks in the pixel block.
-template <typename P>
-__device__ __forceinline__ void team_inverse_job(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0)
+template <typename P, bool SC>
+__device__ __forceinline__ void team_inverse_job(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0, const int32_t* sets)
 {
     const x265hip_cujob& j = L.job;
     TileLds& t = L.tile[0];
@@ -1184,13 +1254,15 @@ __device__ __forceinline__ void team_inverse_job(SlotOut* s, JobLds& L, uint32_t
     const P* src = reinterpret_cast<const P*>(L.pix);
     const P* prd = src + 1024;
     const int16_t* lvIn = reinterpret_cast<const int16_t*>(prd + 1024);
-    const PlaneParams qp = plane_params(j, 0, 5);
+    const PlaneParams qp = plane_params(j, 0, 5, sets);
     const bool stamps = j.reserved != 0;
     uint32_t stamp[6] = { 0, 0, 0, 0, 0, 0 };
     XH_STAMP(0);
     const int tid = threadIdx.x, e = tid * 4;
     x265hip_cujob_unit* un = s->units;
     int fv[4], pv[4], lv[4], dq[4];
+    [[maybe_unused]] int dqs[4];
+    if constexpr (SC) load_table4(qp.dqTab + e, dqs);
     load4(src + e, fv);
     load4(prd + e, pv);
     load4(lvIn + e, lv);
@@ -1202,7 +1274,8 @@ __device__ __forceinline__ void team_inverse_job(SlotOut* s, JobLds& L, uint32_t
         const int d0 = fv[i] - pv[i];
         zeroP += (uint32_t)(d0 * d0);
         cnt += lv[i] != 0;
-        dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
+        if constexpr (SC) dq[i] = dequant_table(lv[i], dqs[i], qp.per, qp.dqShift + 4);
+        else dq[i] = clip3i(-32768, 32767, (lv[i] * qp.dqScale + dqAdd) >> qp.dqShift);
     }
     store4(t.a + e, dq);
     team_part(tm.part2, tid, zeroP);
@@ -1245,8 +1318,9 @@ __device__ __forceinline__ void build_operands(JobLds& L)
 // A job is served by a PAIR of workgroups (two per slot, each alone on a compute unit): role 0 takes the luma units — the 32x32 ones as a team, one after the
 // other, because the submitting thread asks for them one after the other and waits for the first — role 1 the chroma units, a 32x32 tile per wave as before.
 // Every unit is written by exactly one workgroup and carries its own ready words, so the two never meet.
-template <typename P>
-__device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0, int role, bool team)
+// SC: the job names a table set and its units are quantised on the device (run_job)
+template <typename P, bool SC>
+__device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0, int role, bool team, const int32_t* sets)
 {
     const int wv = threadIdx.x >> 6;
     const x265hip_cujob& j = L.job;
@@ -1258,7 +1332,7 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
     const P* prd = src + planeElems;
     if (j.coefMode == X265HIP_CUJOB_INVERSE)
     {
-        if (role == 0) team_inverse_job<P>(s, L, seq, t0);
+        if (role == 0) team_inverse_job<P, SC>(s, L, seq, t0, sets);
         return;
     }
     int sHi, sLo;
@@ -1278,7 +1352,7 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
             const P* ps = plane == 0 ? src : plane == 1 ? src + lumaElems : src + lumaElems + chromaElems;
             const P* pp = plane == 0 ? prd : plane == 1 ? prd + lumaElems : prd + lumaElems + chromaElems;
             const int pw = plane ? NC : N;
-            const PlaneParams qp = plane_params(j, plane, log2n);
+            const PlaneParams qp = plane_params(j, plane, log2n, SC ? sets : nullptr);
             // coefficient mode: a luma tile whose source block is wanted as well is TWO work items (residual part, source part)
             const int parts = j.coefMode && j.sourceDct && plane == 0 ? 2 : 1;
             const int unitBase = x265hipi_cujob_unit_index(&j, sHi, sz, plane, 0, 0);
@@ -1290,7 +1364,7 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
                     for (int part = 0; part < parts; part++)
                     {
                         const int coef = !j.coefMode ? 0 : parts == 1 ? 1 : part == 0 ? 1 | 4 : 2 | 4;
-                        team_chain32<P>(L.tile[0], L.team, ps, pp, pw, u, qp, j.signHide != 0, s->units + unitBase + u, s->levels + elemBase + u * 1024,
+                        team_chain32<P, SC>(L.tile[0], L.team, ps, pp, pw, u, qp, j.signHide != 0, s->units + unitBase + u, s->levels + elemBase + u * 1024,
                                         s->resi + elemBase + u * 1024, seq, t0, j.reserved != 0, coef);
                     }
                 continue;
@@ -1301,12 +1375,12 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
                 const int k = kk / parts;
                 const int coef = !j.coefMode ? 0 : parts == 1 ? 1 : (kk % parts) == 0 ? 1 | 4 : 2 | 4;
                 const int u0 = k * G, count = nUnits - u0 < G ? nUnits - u0 : G;
-                if (log2n == 5) tile_chain<P, 32>(L.tile[wv], L.bop[2], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
+                if (log2n == 5) tile_chain<P, 32, SC>(L.tile[wv], L.bop[2], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
                 else if (log2n == 4 && nUnits == 1 && plane && team)
                     // (the chroma units of a 32x32 CU: one 16x16 unit per plane, the wave's only work)
-                    solo_chain16<P>(L.tile[wv], L.team.op16, ps, pp, qp, j.signHide != 0, s->units + unitBase, s->levels + elemBase, s->resi + elemBase, seq, t0, j.reserved != 0, coef);
-                else if (log2n == 4) tile_chain<P, 16>(L.tile[wv], L.bop[1], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
-                else tile_chain<P, 8>(L.tile[wv], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
+                    solo_chain16<P, SC>(L.tile[wv], L.team.op16, ps, pp, qp, j.signHide != 0, s->units + unitBase, s->levels + elemBase, s->resi + elemBase, seq, t0, j.reserved != 0, coef);
+                else if (log2n == 4) tile_chain<P, 16, SC>(L.tile[wv], L.bop[1], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
+                else tile_chain<P, 8, SC>(L.tile[wv], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
             }
         }
     }
@@ -1622,7 +1696,9 @@ __device__ __forceinline__ void run_intra(SlotOut* s, JobLds& L, uint32_t seq, u
 
 // one job: `ticket` says how many bytes the job holds, so header and pixels arrive in one round trip.  role 0 / 1: this workgroup's half of a CU job (luma /
 // chroma: each fetches the header and its own planes only); SAO statistics and intra scans are role 0's alone
-__device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L, uint32_t ticket, uint64_t* busyTicks, int role, bool team)
+// SETS: the kernel was started for a service with table sets (cu_server_kernel_sets / cu_job_kernel_sets) and holds the SC instantiations beside the flat ones
+template <bool SETS>
+__device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L, uint32_t ticket, uint64_t* busyTicks, int role, bool team, const int32_t* sets)
 {
     const int tid = threadIdx.x;
     const bool cuJob = (ticket & 3) != 3;
@@ -1661,26 +1737,52 @@ __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L
         else if (ij.bitDepth > 8) run_intra<uint16_t>(s, L, ticket, t0);
         else run_intra<uint8_t>(s, L, ticket, t0);
     }
-    else if (ticket & 8) run_tiles<uint16_t>(s, L, ticket, t0, role, team);
-    else run_tiles<uint8_t>(s, L, ticket, t0, role, team);
+    // bit 7 of the ticket: a job with a table set whose units the DEVICE quantises or dequantises (in coefficient mode the host does both: the id is carried and
+    // unused).  Flat jobs run the instantiation they always ran
+    else if (ticket & 128)
+    {
+        // (a kernel that was started without the sets is never given such a job, x265hip_cujob_scaling_add; should it happen the job is given up, not answered
+        // from the flat quantiser)
+        if (!SETS || !sets)
+        {
+            if (tid == 0) __hip_atomic_store(&s->failed, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        else if constexpr (SETS)
+        {
+            if (ticket & 8) run_tiles<uint16_t, true>(s, L, ticket, t0, role, team, sets);
+            else run_tiles<uint8_t, true>(s, L, ticket, t0, role, team, sets);
+        }
+    }
+    else if (ticket & 8) run_tiles<uint16_t, false>(s, L, ticket, t0, role, team, nullptr);
+    else run_tiles<uint8_t, false>(s, L, ticket, t0, role, team, nullptr);
     __syncthreads();
     if (tid == 0)
         *busyTicks += wall_clock64() - t0;
 }
 
-// mode 1: one job, one launch of the pair
+// mode 1: one job, one launch of the pair.  A service without table sets — every encode without scaling lists — launches the kernels it always launched: the
+// flat chains alone, compiled on their own.  Once a set is registered the *_sets kernels take over, which hold the SC instantiations as well (a resident
+// server is started anew at that moment anyway, x265hip_cujob_scaling_add)
 __global__ __launch_bounds__(256) void cu_job_kernel(const SlotIn* sin, SlotOut* s, uint32_t ticket, uint64_t* busyTicks, uint32_t team)
 {
     __shared__ JobLds L;
     build_operands(L);
-    run_job(sin, s, L, ticket, busyTicks + blockIdx.x, (int)blockIdx.x, team != 0);
+    run_job<false>(sin, s, L, ticket, busyTicks + blockIdx.x, (int)blockIdx.x, team != 0, nullptr);
+}
+__global__ __launch_bounds__(256) void cu_job_kernel_sets(const SlotIn* sin, SlotOut* s, uint32_t ticket, uint64_t* busyTicks, uint32_t team, const int32_t* sets)
+{
+    __shared__ JobLds L;
+    build_operands(L);
+    run_job<true>(sin, s, L, ticket, busyTicks + blockIdx.x, (int)blockIdx.x, team != 0, sets);
 }
 
 // mode 0: workgroups 2b and 2b + 1 serve slot b (roles 0 and 1, run_tiles).  The server as a whole leaves when no workgroup has taken a job for `idleTicks` (100 MHz) or the host rings
 // 0xffffffff on any slot: the workgroup that notices sets ctl->quit, every workgroup leaves at its next poll, the last one tells the host.
-__global__ __launch_bounds__(256) void cu_server_kernel(const SlotIn* ins, SlotOut* outs, HostCtl* hostCtl, DevCtl* ctl, uint32_t generation, uint64_t idleTicks)
+// `sets`: the service's table sets as they were when this server was started (x265hip_cujob_scaling_add has every server leave before it writes a set, so the
+// one that reads a set was launched after the set was complete)
+template <bool SETS>
+__device__ __forceinline__ void serve(JobLds& L, const SlotIn* ins, SlotOut* outs, HostCtl* hostCtl, DevCtl* ctl, uint32_t generation, uint64_t idleTicks, const int32_t* sets)
 {
-    __shared__ JobLds L;
     const int role = (int)(blockIdx.x & 1);
     const SlotIn* sin = ins + (blockIdx.x >> 1);
     SlotOut* s = outs + (blockIdx.x >> 1);
@@ -1767,8 +1869,19 @@ __global__ __launch_bounds__(256) void cu_server_kernel(const SlotIn* ins, SlotO
             return;
         }
         last = v;
-        run_job(sin, s, L, v, &ctl->busyTicks[blockIdx.x], role, !((idleTicks >> 62) & 1));
+        run_job<SETS>(sin, s, L, v, &ctl->busyTicks[blockIdx.x], role, !((idleTicks >> 62) & 1), sets);
     }
+}
+__global__ __launch_bounds__(256) void cu_server_kernel(const SlotIn* ins, SlotOut* outs, HostCtl* hostCtl, DevCtl* ctl, uint32_t generation, uint64_t idleTicks)
+{
+    __shared__ JobLds L;
+    serve<false>(L, ins, outs, hostCtl, ctl, generation, idleTicks, nullptr);
+}
+__global__ __launch_bounds__(256) void cu_server_kernel_sets(const SlotIn* ins, SlotOut* outs, HostCtl* hostCtl, DevCtl* ctl, uint32_t generation, uint64_t idleTicks,
+                                                             const int32_t* sets)
+{
+    __shared__ JobLds L;
+    serve<true>(L, ins, outs, hostCtl, ctl, generation, idleTicks, sets);
 }
 
 } // namespace
@@ -1802,6 +1915,9 @@ struct x265hip_cuserve
     std::mutex launchLock;
     std::atomic<uint64_t> jobs{ 0 }, starts{ 0 }, bytes{ 0 }, saoJobs{ 0 }, intraJobs{ 0 };
     std::atomic<int> paused{ 0 };                 // servers_pause() callers in progress: no server is started meanwhile
+    int32_t* sets = nullptr;                      // device memory: X265HIP_CUJOB_SCALING_SETS table sets of kSetInts int32 (x265hip_cujob_scaling_add; allocated with the first)
+    std::atomic<uint32_t> nsets{ 0 };             // sets registered: ids 1 .. nsets are valid in x265hip_cujob::scaling
+    std::mutex setLock;
     uint64_t idleUs = 2000;
 };
 static std::mutex g_openLock;
@@ -1831,8 +1947,12 @@ static int start_server(x265hip_cuserve* cs)
     hipError_t e = hipMemsetAsync(cs->ctl, 0, 8, cs->serverStream);
     if (e == hipSuccess)
     {
-        hipLaunchKernelGGL(cu_server_kernel, dim3(2 * cs->slots), dim3(256), 0, cs->serverStream, cs->inDev, cs->outDev, cs->devHostCtl, cs->ctl, gen ? gen : 1u,
-                           cs->idleUs * 100 | (getenv("X265HIP_CUSERVE_SPIN") && atoi(getenv("X265HIP_CUSERVE_SPIN")) ? 1ull << 63 : 0ull) | (team_off() ? 1ull << 62 : 0ull));
+        const uint64_t idle = cs->idleUs * 100 | (getenv("X265HIP_CUSERVE_SPIN") && atoi(getenv("X265HIP_CUSERVE_SPIN")) ? 1ull << 63 : 0ull) | (team_off() ? 1ull << 62 : 0ull);
+        if (cs->sets)
+            hipLaunchKernelGGL(cu_server_kernel_sets, dim3(2 * cs->slots), dim3(256), 0, cs->serverStream, cs->inDev, cs->outDev, cs->devHostCtl, cs->ctl, gen ? gen : 1u, idle,
+                               (const int32_t*)cs->sets);
+        else
+            hipLaunchKernelGGL(cu_server_kernel, dim3(2 * cs->slots), dim3(256), 0, cs->serverStream, cs->inDev, cs->outDev, cs->devHostCtl, cs->ctl, gen ? gen : 1u, idle);
         e = hipGetLastError();
     }
     if (cur >= 0 && cur != cs->device) (void)hipSetDevice(cur);
@@ -2039,6 +2159,7 @@ int x265hip_cuserve_close(x265hip_cuserve* cs)
     delete[] cs->shadow;
     if (cs->hostCtl) (void)hipHostFree(cs->hostCtl);
     if (cs->ctl) (void)device_free(cs->ctl);
+    if (cs->sets) (void)device_free(cs->sets);
     if (cs->serverStream) (void)hipStreamDestroy(cs->serverStream);
     delete[] cs->seq; delete[] cs->jobStreams;
     delete cs;
@@ -2067,13 +2188,25 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
     if (j.log2CUSize < 4 || j.log2CUSize > 6 || x265hipi_cujob_levels(&j, &sHi, &sLo) < 1 || !valid_depth((int)j.bitDepth) || j.chroma > 3)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: CU 2^%u, transform sizes 2^%u..2^%u, depth %u, chroma format %u", j.log2CUSize, j.log2TrMin, j.log2TrMax,
                          j.bitDepth, j.chroma);
+    // a table set: one that is registered, and quantiser parameters that stay inside its matrices (rem picks the matrix, per is a shift count)
+    if (j.scaling)
+    {
+        bool ok = j.scaling <= cs->nsets.load(std::memory_order_acquire);
+        for (int p = 0; ok && p < (j.chroma ? 3 : 1); p++)
+            ok = j.qpRem[p] >= 0 && j.qpRem[p] < 6 && j.qpPer[p] >= 0 && j.qpPer[p] < 16;
+        if (!ok)
+            return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: table set %u (%u registered), rem %d %d %d, per %d %d %d", j.scaling, cs->nsets.load(), j.qpRem[0], j.qpRem[1],
+                             j.qpRem[2], j.qpPer[0], j.qpPer[1], j.qpPer[2]);
+    }
     uint32_t run = cs->seq[slot].load(std::memory_order_relaxed) + 1;                       // a slot has one submitter at a time
     if (run >= 0xfffff0u) run = 1;
     cs->seq[slot].store(run, std::memory_order_relaxed);
     const bool inverseJob = j.coefMode == X265HIP_CUJOB_INVERSE;
     if (inverseJob && (j.log2CUSize != 5 || j.chroma || sHi != 5))
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: an inverse job is one 32x32 luma unit (CU 2^%u, chroma %u, transform 2^%d)", j.log2CUSize, j.chroma, sHi);
-    const uint32_t seq = (run << 8) | (j.log2CUSize - 4) | (j.chroma ? 4u | ((j.chroma - 1) << 5) : 0u) | (j.bitDepth > 8 ? 8u : 0u) | (inverseJob ? 16u : 0u);
+    // (bit 7: the device quantises or dequantises with a table set — not in coefficient mode, where the id is carried unused)
+    const uint32_t seq = (run << 8) | (j.log2CUSize - 4) | (j.chroma ? 4u | ((j.chroma - 1) << 5) : 0u) | (j.bitDepth > 8 ? 8u : 0u) | (inverseJob ? 16u : 0u) |
+                         (j.scaling && (!j.coefMode || inverseJob) ? 128u : 0u);
     *seqOut = seq;
     cs->jobs.fetch_add(1, std::memory_order_relaxed);
     {
@@ -2089,7 +2222,11 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
         int cur = -1;
         (void)hipGetDevice(&cur);
         if (cur != cs->device) (void)hipSetDevice(cs->device);
-        hipLaunchKernelGGL(cu_job_kernel, dim3(2), dim3(256), 0, cs->jobStreams[slot], cs->inDev + slot, cs->outDev + slot, seq, &cs->ctl->busyTicks[2 * slot], team_off() ? 0u : 1u);
+        if (cs->sets)
+            hipLaunchKernelGGL(cu_job_kernel_sets, dim3(2), dim3(256), 0, cs->jobStreams[slot], cs->inDev + slot, cs->outDev + slot, seq, &cs->ctl->busyTicks[2 * slot],
+                               team_off() ? 0u : 1u, (const int32_t*)cs->sets);
+        else
+            hipLaunchKernelGGL(cu_job_kernel, dim3(2), dim3(256), 0, cs->jobStreams[slot], cs->inDev + slot, cs->outDev + slot, seq, &cs->ctl->busyTicks[2 * slot], team_off() ? 0u : 1u);
         const hipError_t le = hipGetLastError();
         if (cur >= 0 && cur != cs->device) (void)hipSetDevice(cur);
         if (le != hipSuccess) return check_hip(le, "cu_job_kernel");
@@ -2105,6 +2242,55 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
 uint32_t x265hip_cujob_formats(void)
 {
     return 0xFu;                                                                             // 4:0:0, 4:2:0, 4:2:2, 4:4:4 (x265hip_cujob::chroma)
+}
+
+uint32_t x265hip_cujob_features(void)
+{
+    return 1u;                                                                               // bit 0: table sets of scaling lists (x265hip_cujob::scaling)
+}
+
+int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id)
+{
+    if (!cs || !quantCoef || !dequantCoef || !id) return set_error(X265HIP_EINVAL, "x265hip_cujob_scaling_add: null");
+    std::lock_guard<std::mutex> g(cs->setLock);
+    const uint32_t n = cs->nsets.load();
+    if (n >= X265HIP_CUJOB_SCALING_SETS)
+        return set_error(X265HIP_EINVAL, "x265hip_cujob_scaling_add: %d table sets are registered already", X265HIP_CUJOB_SCALING_SETS);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != cs->device && hipSetDevice(cs->device) != hipSuccess)
+        return set_error(X265HIP_EHIP, "x265hip_cujob_scaling_add: hipSetDevice(%d) failed", cs->device);
+    // A resident server may hold stale cache lines of the memory the set goes to (the L2 of its XCD is not coherent with another agent's writes, a compute
+    // unit's L1 never is) and gets no chance to drop them while it runs.  So every server leaves first (jobs in progress are finished, waiters see
+    // x265hip_cuserve_poke == 1), the set is written and the device synchronised, and whoever submits next starts a server: a kernel launched after the
+    // copy was complete, which HIP's ordering of a launch behind a finished copy makes a reader of the new contents.  Mode 1 launches per job anyway.
+    servers_pause();
+    int e = X265HIP_OK;
+    if (cs->mode == 0)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        while (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(10))
+            __builtin_ia32_pause();
+        if (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0)
+            e = set_error(X265HIP_EHIP, "x265hip_cujob_scaling_add: the resident server did not leave");
+    }
+    if (!e && !cs->sets)
+    {
+        e = check_hip(hipMalloc((void**)&cs->sets, sizeof(int32_t) * kSetInts * X265HIP_CUJOB_SCALING_SETS), "hipMalloc(cuserve table sets)");
+        if (e) cs->sets = nullptr;
+    }
+    if (!e) e = check_hip(hipMemcpy(cs->sets + (size_t)n * kSetInts, quantCoef, sizeof(int32_t) * X265HIP_CUJOB_SCALING_ENTRIES, hipMemcpyHostToDevice), "hipMemcpy(quantiser tables)");
+    if (!e) e = check_hip(hipMemcpy(cs->sets + (size_t)n * kSetInts + X265HIP_CUJOB_SCALING_ENTRIES, dequantCoef, sizeof(int32_t) * X265HIP_CUJOB_SCALING_ENTRIES, hipMemcpyHostToDevice),
+                          "hipMemcpy(dequantiser tables)");
+    if (!e) e = check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize(cuserve table sets)");
+    if (!e)
+    {
+        cs->nsets.store(n + 1, std::memory_order_release);
+        *id = n + 1;
+    }
+    servers_resume();
+    if (cur >= 0 && cur != cs->device) (void)hipSetDevice(cur);
+    return e;
 }
 
 uint32_t x265hip_saojob_depths(void)

@@ -193,6 +193,8 @@ PROTOTYPES = {
     "x265hip_cuserve_submit_sao": (i32, [vp, i32, vp, vp]),
     "x265hip_saojob_depths": (u32, []),
     "x265hip_cujob_formats": (u32, []),
+    "x265hip_cujob_features": (u32, []),
+    "x265hip_cujob_scaling_add": (i32, [vp, vp, vp, C.POINTER(u32)]),
     "x265hip_cuserve_submit_intra": (i32, [vp, i32, vp, vp]),
     "x265hip_cuserve_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     "x265hip_device_time": (i32, [i32, vp, vp, vp]),
@@ -265,7 +267,7 @@ class CuJob(C.Structure):
     """x265hip_cujob (include/x265hip.h): the header of a CU residual quad-tree job"""
     _fields_ = [("log2CUSize", u32), ("log2TrMax", u32), ("log2TrMin", u32), ("chroma", u32), ("bitDepth", u32), ("quantOffset", u32), ("signHide", u32),
                 ("reserved", u32), ("qpRem", C.c_int32 * 3), ("qpPer", C.c_int32 * 3), ("quantScale", C.c_int32 * 3), ("dequantScale", C.c_int32 * 3),
-                ("coefMode", u32), ("sourceDct", u32)]
+                ("coefMode", u32), ("sourceDct", u32), ("scaling", u32)]
 
 
 class SaoJobPlane(C.Structure):

@@ -13,8 +13,9 @@
 // (a mailbox slot in page-locked memory; x265_amd/csrc/cuserve.hip), and while the reference's own estimateResidualQT body runs on this
 // thread, Quant::transformNxN / ::invtransformNxN called for a residual block of that CU copy the device's result instead of computing it.
 // Same values either way (tests/test_cuserve.py pins the device against the oracle's restatement of those two functions, which is pinned
-// against the reference's); anything the job does not cover (transform skip, transquant bypass, scaling lists, noise reduction)
-// runs the reference's functions as before.  Every chroma format is served (x265hip_cujob::chroma = the encoder's csp): a 4:2:2 chroma plane is N/2 x N with
+// against the reference's); anything the job does not cover (transform skip, transquant bypass, noise reduction, a scaling list with an entry below 8)
+// runs the reference's functions as before.  An encode with scaling lists hands its quantiser and dequantiser matrices to the service once, as a table set
+// (scaling_id below), and its jobs name the set.  Every chroma format is served (x265hip_cujob::chroma = the encoder's csp): a 4:2:2 chroma plane is N/2 x N with
 // the reference's two square sub-TUs per transform unit (search.cpp:3388-3393) as two rows of job units, a 4:4:4 one N x N with units of the luma size.
 //
 // Beside the transforms the job answers the distortions of the same blocks — cu[].sse_pp(source, prediction) and cu[].sse_pp(source, reconstruction)
@@ -47,6 +48,7 @@ std::atomic<int> g_lateJobs(0);
 int g_invJobs = X265_DEPTH == 8 ? 1 : 0;
 int g_rdoqJobs = 1;              // X265HIP_CUSERVE_RDOQ=0: CUs quantised by Quant::rdoQuant are not handed over (round 4's behaviour).  On: measured on the MI355X box at
                                  // BASELINE configs[2] / configs[3] (profiles/r05_v1_configs*_ab.txt): +2 % / +6 % fps, -3 % / -6 % CPU seconds
+int g_scaling = 1;               // X265HIP_CUSERVE_SCALING=0: CUs of an encode with scaling lists are not handed over (what the binding did before table sets existed)
 int g_formats = 1;               // X265HIP_CUSERVE_FORMATS=0: CUs of 4:2:2 / 4:4:4 pictures are not handed over (what the binding did before their jobs existed)
 int g_slots = 64;                // X265HIP_CUSERVE_SLOTS: jobs that can be in flight (default: twice the CPUs this process may use, 16..64)
 bool g_verify = false;           // X265HIP_VERIFY=1: every served unit is recomputed by the reference's function and compared
@@ -61,7 +63,7 @@ std::atomic<bool> g_dead(false); // the device failed once: every later CU is co
 std::atomic<uint64_t> g_cycles[18][2], g_calls[18][2];
 __attribute__((tls_model("initial-exec"))) thread_local int t_inRqt = 0;
 
-struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs; };
+struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs, scalingJobs, scalingKept; };
 Counters g_count[64];
 std::atomic<int> g_nextShard(0);
 __attribute__((tls_model("initial-exec"))) thread_local int t_shard = -1;
@@ -134,6 +136,8 @@ void report_time()
                         (double)g_cycles[k][w].load() / g_calls[k][w].load(), g_cycles[k][w].load() * 1e-9);
     }
 }
+
+int scaling_sets();
 
 void report()
 {
@@ -215,6 +219,13 @@ void report()
             fprintf(stderr, "x265hip: cuserve: %llu of the jobs were CUs of a 4:2:2 / 4:4:4 picture (4:2:2: the two CU-level N/2 x N chroma calls, sse_pp and sub_ps, "
                             "stay on the host; every transform unit is served)\n", (unsigned long long)fj);
     }
+    {
+        uint64_t sj = 0, sk2 = 0;
+        for (int i = 0; i < 64; i++) { sj += g_count[i].scalingJobs; sk2 += g_count[i].scalingKept; }
+        if (sj || sk2 || scaling_sets())
+            fprintf(stderr, "x265hip: cuserve: scaling lists: %d sets registered, %llu jobs carried one, %llu CUs kept on the host because of their list\n", scaling_sets(),
+                    (unsigned long long)sj, (unsigned long long)sk2);
+    }
     if (dsb || dad)
         fprintf(stderr, "x265hip: cuserve: %llu sub_ps and %llu add_ps calls of those CUs put off because only the job's answers read their results (%llu + %llu run after all)\n",
                 (unsigned long long)dsb, (unsigned long long)dad, (unsigned long long)lsb, (unsigned long long)lad);
@@ -239,6 +250,7 @@ bool decide()
         if (getenv("X265HIP_CUSERVE_RDOQ")) g_rdoqJobs = atoi(getenv("X265HIP_CUSERVE_RDOQ")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_INVERSE")) g_invJobs = atoi(getenv("X265HIP_CUSERVE_INVERSE")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_FORMATS")) g_formats = atoi(getenv("X265HIP_CUSERVE_FORMATS")) ? 1 : 0;
+        if (getenv("X265HIP_CUSERVE_SCALING")) g_scaling = atoi(getenv("X265HIP_CUSERVE_SCALING")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_TIMEOUT_MS") && atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) > 0) g_timeoutNs = atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) * 1000000ll;
         if (getenv("X265HIP_CUSERVE_SLOTS")) g_slots = atoi(getenv("X265HIP_CUSERVE_SLOTS"));
         else
@@ -450,6 +462,93 @@ inline bool wait_word(Job& j, const uint32_t* ready, int site)
 
 } // namespace cusvc
 
+extern std::atomic<uint64_t> g_x265hipEncoderEpoch;          // x265_hip_refraces.cpp
+
+namespace cusvc {
+
+// ---- scaling lists: the encoder's matrices as table sets of the services ------------------------------------------------------------------------------------
+// A set = m_quantCoef / m_dequantCoef [sizes 8..32][inter lists Y, Cb, Cr][rem] as the encoder's ScalingList holds them (scalinglist.cpp:342-415), packed in the
+// order x265hip_cujob_scaling_add takes them.  Sets are shared by CONTENT: the encoders of an ABR ladder, or one encoder after another with the same lists,
+// name one set.  A set is registered on every service at once, under one lock and in the same order, so its id is the same at every place.
+struct PackedSet { int32_t* tab; uint32_t id; };            // tab: quantiser entries, then dequantiser entries
+PackedSet g_sets[X265HIP_CUJOB_SCALING_SETS];
+int g_nsets = 0;                                             // (under g_lock)
+bool g_setsFull = false;                                     // a registration failed: no further one is tried
+int scaling_sets() { std::lock_guard<std::mutex> g(g_lock); return g_nsets; }
+// what this thread found out last: the ScalingList at `list` had set `id` (0: its CUs stay on the host) when the encoder epoch was `epoch`.  An address says
+// nothing across encoders — a later one may get the block an earlier one freed — so an answer older than the newest encoder's workers is looked up again by
+// content (every encoder bumps the epoch when it constructs its Analysis objects, before it analyses a CU)
+__attribute__((tls_model("initial-exec"))) thread_local const ScalingList* t_list = NULL;
+__attribute__((tls_model("initial-exec"))) thread_local uint64_t t_listEpoch = 0;
+__attribute__((tls_model("initial-exec"))) thread_local uint32_t t_listId = 0;
+__attribute__((tls_model("initial-exec"))) thread_local bool t_listKept = false;      // the last make_header refused its CU because of the list
+
+uint32_t scaling_lookup(const ScalingList* sl)
+{
+    // quant_c multiplies abs(coef) * quantCoef in int (dct.cpp:676): with every entry >= 8 the product stays below 2^31 for any 16-bit coefficient, below that
+    // the reference's own arithmetic is undefined — such a list is not served
+    for (int size = 0; size < ScalingList::NUM_SIZES; size++)
+        for (int list = 0; list < ScalingList::NUM_LISTS; list++)
+        {
+            const int count = size ? 64 : 16;
+            for (int i = 0; i < count; i++)
+                if (sl->m_scalingListCoef[size][list][i] < 8) return 0;
+            if (size >= 2 && sl->m_scalingListDC[size][list] < 8) return 0;
+        }
+    const size_t ints = X265HIP_CUJOB_SCALING_ENTRIES;
+    int32_t* tab = (int32_t*)malloc(sizeof(int32_t) * 2 * ints);
+    if (!tab) return 0;
+    size_t at = 0;
+    for (int size = 1; size <= 3; size++)
+        for (int plane = 0; plane < 3; plane++)
+            for (int rem = 0; rem < 6; rem++, at += (size_t)16 << (2 * size))
+            {
+                memcpy(tab + at, sl->m_quantCoef[size][3 + plane][rem], sizeof(int32_t) * (16 << (2 * size)));
+                memcpy(tab + ints + at, sl->m_dequantCoef[size][3 + plane][rem], sizeof(int32_t) * (16 << (2 * size)));
+            }
+    // (the entries were looked at above; the tables are what the device multiplies with: 0 < quantCoef <= (26214 << 4) / 8)
+    for (size_t i = 0; i < ints; i++)
+        if (tab[i] < 1 || tab[i] > 52428) { free(tab); return 0; }
+    std::lock_guard<std::mutex> g(g_lock);
+    for (int k = 0; k < g_nsets; k++)
+        if (!memcmp(g_sets[k].tab, tab, sizeof(int32_t) * 2 * ints)) { free(tab); return g_sets[k].id; }
+    if (g_setsFull || g_nsets >= X265HIP_CUJOB_SCALING_SETS || g_dead.load()) { free(tab); return 0; }
+    uint32_t id = 0;
+    const int nsvc = g_nsvc.load();
+    for (int k = 0; k < nsvc; k++)
+    {
+        uint32_t got = 0;
+        if (x265hip_cujob_scaling_add(g_svc[k].cs, tab, tab + ints, &got) || !got || (k && got != id))
+        {
+            // no free set at some place (somebody else registers sets on it), or the device failed: this list and every later one stay on the host
+            g_setsFull = true;
+            free(tab);
+            return 0;
+        }
+        id = got;
+    }
+    if (!id) { free(tab); return 0; }
+    g_sets[g_nsets].tab = tab; g_sets[g_nsets].id = id;
+    g_nsets++;
+    return id;
+}
+
+// the table set of this encoder's scaling lists, or 0: the CU stays on the host
+inline uint32_t scaling_id(const ScalingList* sl)
+{
+    const uint64_t epoch = g_x265hipEncoderEpoch.load(std::memory_order_acquire);
+    if (sl == t_list && epoch == t_listEpoch)
+        return t_listId;
+    uint32_t id = 0;
+    // only a library that takes table sets gets them (an older one, or the emulated one of the tests, has neither symbol)
+    if (g_scaling && x265hip_cujob_features && x265hip_cujob_scaling_add && (x265hip_cujob_features() & 1) && service())
+        id = scaling_lookup(sl);
+    t_list = sl; t_listEpoch = epoch; t_listId = id;
+    return id;
+}
+
+} // namespace cusvc
+
 using namespace cusvc;
 namespace {
 
@@ -462,14 +561,23 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
     const bool codeChroma = csp != X265_CSP_I400 && se->m_frame->m_fencPic->m_picCsp != X265_CSP_I400;
     // RDOQ (presets slow / slower): the quantiser is Quant::rdoQuant and stays on the host (its decisions read the entropy coder's state); the job carries
     // the transforms in front of it — coefficient mode (X265HIP_CUSERVE_RDOQ=0 switches it off)
-    if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || (q.m_nr && q.m_nr->offset) || q.m_scalingList->m_bEnabled || csp < X265_CSP_I400 || csp > X265_CSP_I444 ||
+    t_listKept = false;
+    if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || (q.m_nr && q.m_nr->offset) || csp < X265_CSP_I400 || csp > X265_CSP_I444 ||
         (csp != X265_CSP_I400) != codeChroma)
         return false;
     // 4:2:2 / 4:4:4: only a library that says it takes such jobs gets them (an older one, or the emulated one of the tests, has no x265hip_cujob_formats: these
     // CUs then stay on the host, as they do with X265HIP_CUSERVE_FORMATS=0)
     if (csp > X265_CSP_I420 && (!g_formats || !x265hip_cujob_formats || !((x265hip_cujob_formats() >> csp) & 1)))
         return false;
+    // scaling lists: the job names the table set that holds this encoder's matrices (scaling_id); a list the device does not serve keeps its CUs on the host
+    uint32_t set = 0;
+    if (q.m_scalingList->m_bEnabled && !(set = scaling_id(q.m_scalingList)))
+    {
+        t_listKept = true;
+        return false;
+    }
     memset(&hdr, 0, sizeof(hdr));
+    hdr.scaling = set;
     hdr.log2CUSize = log2CUSize; hdr.log2TrMax = depthRange[1]; hdr.log2TrMin = depthRange[0];
     hdr.chroma = codeChroma ? csp : 0; hdr.bitDepth = X265_DEPTH;         // (X265_CSP_I420..I444 are the job's format numbers)
     hdr.quantOffset = cu.m_slice->m_sliceType == I_SLICE ? 171 : 85;
@@ -479,6 +587,7 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
     {
         const QpParam& qp = q.m_qpParam[p];
         hdr.qpRem[p] = qp.rem; hdr.qpPer[p] = qp.per;
+        if (set) continue;                                                              // (the set's matrices are the scales)
         hdr.quantScale[p] = q.m_scalingList->m_quantCoef[3][3 + p][qp.rem][0];          // flat: every entry of every size and list is s_quantScales[rem]
         hdr.dequantScale[p] = ScalingList::s_invQuantScales[qp.rem];
     }
@@ -632,6 +741,7 @@ bool submit(Search* se, Mode& mode, uint32_t log2CUSize, ShortYuv& resiYuv, cons
     j.active = true;
     counters().jobs.fetch_add(1, std::memory_order_relaxed);
     if (hdr.chroma > 1) counters().formatJobs.fetch_add(1, std::memory_order_relaxed);
+    if (hdr.scaling) counters().scalingJobs.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -1229,7 +1339,10 @@ void Search::encodeResAndCalcRdInterCU(Mode& interMode, const CUGeom& cuGeom)
         uint32_t range[2];
         interMode.cu.getInterTUQtDepthRange(range, 0);
         if (!submit(this, interMode, cuGeom.log2CUSize, m_rqt[cuGeom.depth].tmpResiYuv, range))
+        {
             counters().skipped.fetch_add(1, std::memory_order_relaxed);
+            if (t_listKept) counters().scalingKept.fetch_add(1, std::memory_order_relaxed);
+        }
         else
             t_job.inTree = false;
     }

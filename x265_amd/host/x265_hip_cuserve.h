@@ -36,6 +36,9 @@
 
 // not in every library these seams are linked against (the emulated one of the tests, an older libx265hip): absent = 4:2:0 and 4:0:0 jobs only
 extern "C" uint32_t x265hip_cujob_formats(void) __attribute__((weak));
+// likewise: absent (or bit 0 clear) = no table sets, CUs of an encode with scaling lists stay on the host
+extern "C" uint32_t x265hip_cujob_features(void) __attribute__((weak));
+extern "C" int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id) __attribute__((weak));
 
 namespace X265_NS {
 

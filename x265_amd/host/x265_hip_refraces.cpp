@@ -20,7 +20,14 @@
 #undef protected
 #undef private
 
+#include <atomic>
+
 namespace X265_NS {
+
+// Bumped whenever an encoder builds its analysis workers, i.e. at least once between the end of one encoder and the first CU of the next.  What the
+// bindings remember per address of an encoder-owned object (the scaling list tables of x265_hip_cuserve.cpp) is looked at again when this has moved: a
+// later encoder may have been given the address an earlier one had.
+std::atomic<uint64_t> g_x265hipEncoderEpoch(1);
 
 // the reference's constructor body (analysis.cpp:73-83) and the plain members it leaves out
 Analysis::Analysis()
@@ -45,6 +52,7 @@ Analysis::Analysis()
     cacheCost = NULL;
     m_additionalCtuInfo = NULL;
     m_prevCtuInfoChange = NULL;
+    g_x265hipEncoderEpoch.fetch_add(1, std::memory_order_release);
 }
 
 } // namespace X265_NS
