@@ -836,8 +836,9 @@ int x265hip_call_frame_init_lowres(int depth, const void* src, int64_t srcStride
  * that the device reads and writes directly: the caller fills the slot's job header and pixel block, submits, and polls the
  * per-unit `ready` / `readyInv` words (each unit's forward half — numSig and levels — is published as soon as it is done, luma first;
  * its inverse half follows).  Flat quantiser, or the quantiser and dequantiser matrices of a scaling list from a table set registered on the
- * service (x265hip_cujob::scaling, x265hip_cujob_scaling_add); no transform skip, no transquant bypass, no noise reduction: the caller does
- * not submit such CUs.  RDOQ: coefficient mode (x265hip_cujob::coefMode).
+ * service (x265hip_cujob::scaling, x265hip_cujob_scaling_add); noise reduction (--nr-inter / --nr-intra: denoiseDct between the transform and the
+ * quantiser) with the offset tables the job carries (X265HIP_CUJOB_DENOISE, x265hip_cujob_denoise); no transform skip, no transquant bypass: the
+ * caller does not submit such CUs.  RDOQ: coefficient mode (x265hip_cujob::coefMode).
  *
  * Chroma format of a job (x265hip_cujob::chroma, the values of X265_CSP_I400..I444) and its chroma shifts hs / vs: 0 no chroma, 1 4:2:0 (1 / 1),
  * 2 4:2:2 (1 / 0), 3 4:4:4 (0 / 0); x265hip_cujob_formats() tells which of them the library accepts.
@@ -877,6 +878,13 @@ typedef struct x265hip_cujob
  * pixel block: the unit's source block, its prediction, then its 1 024 levels (int16, rows contiguous).  Results in units[0]: numSig (non-zero levels counted),
  * zeroDist, codedDist, codedEnergy and the unit's `resi` block; readyInv, then ready. */
 #define X265HIP_CUJOB_INVERSE 8u
+/* OR-ed into coefMode (0 or 1: the valid values are 0, 1, 16 and 17; an inverse job has nothing to denoise): noise reduction.  Behind cu[].dct every unit's
+ * residual coefficients pass denoiseDct (reference common/dct.cpp:744-755, called from quant.cpp:444-451) with the offset table of the unit's category —
+ * a = |c|; d = a - offset[i]; c = d < 0 ? 0 : sign(c) * d — taken from the block the caller wrote at x265hip_cujob_denoise's *offsets; the quantiser (or, in
+ * coefficient mode, the `levels` block) gets the denoised coefficients, the slot's absCoef array the |c| before denoise: what the reference adds to
+ * residualSum[category], which the caller does for the calls it answers.  The source block's transform (sourceDct) is not denoised; zeroDist is what it was.
+ * x265hip_cujob_features() bit 1. */
+#define X265HIP_CUJOB_DENOISE 16u
 typedef struct x265hip_cujob_unit
 {
     uint32_t ready;               /* == the job's ticket once this unit's numSig, zeroDist and levels are in place (the forward half) */
@@ -934,9 +942,31 @@ X265HIP_HD static inline int x265hipi_cujob_elem_offset(const x265hip_cujob* j, 
     off += N2 + (plane == 2 ? cElems : 0);
     return off + (t << (2 * (s - x265hipi_cujob_hshift(j->chroma))));
 }
+/* the offset block of a denoise job (x265hip_cujob_denoise): the tables of the categories the job's units use, [luma sHi][luma sLo][chroma sHi - hs]
+ * [chroma sLo - hs], n * n uint16 each (Cb and Cr share a category); absent levels and planes are left out.  Entries of the whole block, and where the
+ * table of the units of plane `plane` at the level of luma size s starts */
+#define X265HIP_CUJOB_DENOISE_ENTRIES (2 * (1024 + 256))   /* 4:4:4, 64x64, two levels */
+X265HIP_HD static inline int x265hipi_cujob_denoise_entries(const x265hip_cujob* j, int sHi, int sLo)
+{
+    const int hs = x265hipi_cujob_hshift(j->chroma);
+    int n = 0;
+    for (int s = sHi; s >= sLo; s--)
+        n += (1 << (2 * s)) + (j->chroma ? 1 << (2 * (s - hs)) : 0);
+    return n;
+}
+X265HIP_HD static inline int x265hipi_cujob_denoise_offset(const x265hip_cujob* j, int sHi, int sLo, int s, int plane)
+{
+    const int hs = plane ? x265hipi_cujob_hshift(j->chroma) : 0;
+    int off = 0;
+    if (plane)
+        for (int k = sHi; k >= sLo; k--) off += 1 << (2 * k);
+    for (int k = sHi; k > s; k--) off += 1 << (2 * (k - hs));
+    return off;
+}
 /* the chroma formats this library's CU jobs accept: bit f set for x265hip_cujob::chroma == f (0xF here).  Needs no device. */
 uint32_t x265hip_cujob_formats(void);
-/* what else this library's CU jobs can do: bit 0 = table sets of scaling lists (x265hip_cujob::scaling).  Needs no device. */
+/* what else this library's CU jobs can do: bit 0 = table sets of scaling lists (x265hip_cujob::scaling), bit 1 = noise reduction (X265HIP_CUJOB_DENOISE,
+ * x265hip_cujob_denoise).  Needs no device. */
 uint32_t x265hip_cujob_features(void);
 /* A table set = the quantiser and dequantiser matrices of the inter lists a job uses, packed [size 8, 16, 32][plane Y, Cb, Cr][rem 0..5][n * n] (rows
  * contiguous: ScalingList::m_quantCoef / m_dequantCoef [1..3][3..5][0..5] as the encoder holds them, scalinglist.cpp:342-415).  quant_c multiplies in int:
@@ -971,6 +1001,15 @@ int x265hip_cuserve_stats(x265hip_cuserve* cs, uint64_t* jobs, uint64_t* serverS
  * more than X265HIP_CUJOB_SCALING_SETS: X265HIP_EINVAL, the service goes on serving.  A resident server is made to leave and start again around the copy
  * (waiters see x265hip_cuserve_poke == 1 meanwhile), so that the tables are first read by a kernel launched after they were written. */
 int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id);
+/* (optional like x265hip_cujob_scaling_add) the two blocks of the slot a denoise job uses beside x265hip_cuserve_slot's:
+ * *offsets: X265HIP_CUJOB_DENOISE_ENTRIES uint16 of the slot's input half, write-only like `pixels` (device memory through the large BAR: written front to
+ * back before the submit, never read): the offset tables of the job's categories in the order of x265hipi_cujob_denoise_offset.  The offsets travel with the job:
+ * nothing is cached on the device, and a job without the flag reads nothing of the block.
+ * *absCoef: a third output array beside `levels` / `resi` (page-locked host memory, X265HIP_CUJOB_MAX_ELEMS uint16): |coefficient before denoise| of every unit
+ * of a denoise job at the unit's x265hipi_cujob_elem_offset, in place when the unit's `ready` word is.
+ * The first call on a service has its kernels replaced by the ones that hold the denoise step (a resident server leaves and starts again, as around
+ * x265hip_cujob_scaling_add: once per service); a job with the flag on a service that never saw this call is X265HIP_EINVAL at submit. */
+int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef);
 
 /* ---- SAO statistics of one CTU as a job of the same service (round 5) ---------------------------------------------------------------------
  * SAO::calcSaoStatsCTU (reference source/encoder/sao.cpp:735-917; called per plane from rdoSaoUnitCu :1293-1305) measures, for the deblocked CTU, the

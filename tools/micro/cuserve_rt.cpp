@@ -3,6 +3,8 @@
 //   cuserve_rt <mode 0|1> [iters] [stamps 0|1]   1, 4 and 16 submitting threads; 32x32 and 64x64 CUs (4:2:0, 8 bit, one transform size);
 //                                                stamps 1: the chain's stage stamps (job.reserved, x265hip_cujob_unit::reserved) of the first luma and the first Cb unit
 //   CUSERVE_RT_SAO_DEPTH=10|12: the SAO statistics jobs at that depth (16-bit samples), one luma plane per job as the seam sends them
+//   last: the 32x32 job as a DENOISE job (X265HIP_CUJOB_DENOISE: 2.5 KB of offsets through the BAR in front of the doorbell, 3 KB of |coefficient| read back), and
+//   the plain 32x32 job once more on the service the denoise call has switched over (CUSERVE_RT_ONLY=dn: these two alone)
 #include <atomic>
 #include <algorithm>
 #include <chrono>
@@ -25,10 +27,9 @@ int main(int argc, char** argv)
     // CUSERVE_RT_ONLY=cu5|cu6|sao, CUSERVE_RT_THREADS=<n>: one job shape from one thread count — the counter passes (tools/exp/gpu.sh pmc) want launches of one kind
     const char* only = getenv("CUSERVE_RT_ONLY");
     const int onlyT = getenv("CUSERVE_RT_THREADS") ? atoi(getenv("CUSERVE_RT_THREADS")) : 0;
-    for (int log2cu = 5; log2cu <= 6; log2cu++)
-        for (int T : { 1, 4, 16 })
+    // dn: 0 a plain job; 1 a denoise job; 2 a plain job after the service was switched over
+    auto run_cu = [&](int log2cu, int T, int dn) -> bool
         {
-            if ((only && (only[0] != 'c' || only[2] != '0' + log2cu)) || (onlyT && T != onlyT)) continue;
             std::vector<std::vector<double>> lat(T), first(T), dev(T);
             std::vector<std::vector<double>> st[2][7];
             for (auto& a : st) for (auto& b : a) b.resize(T);
@@ -42,6 +43,12 @@ int main(int argc, char** argv)
                 std::vector<unsigned char> src(bytes);
                 uint32_t s = 1234 + t;
                 for (auto& b : src) { s = s * 1664525u + 1013904223u; b = (unsigned char)(128 + ((s >> 24) & 15)); }
+                // a denoise job's offsets: what a frame's sums turn into at everyday strengths, DC 0 (luma 32x32, then chroma 16x16)
+                uint16_t* offsets = NULL; const uint16_t* absCoef = NULL;
+                std::vector<uint16_t> tabs(1024 + 256);
+                for (auto& o : tabs) { s = s * 1664525u + 1013904223u; o = (uint16_t)((s >> 24) & 7); }
+                tabs[0] = tabs[1024] = 0;
+                if (dn == 1 && x265hip_cujob_denoise(cs, t, &offsets, &absCoef)) { fprintf(stderr, "denoise: %s\n", x265hip_last_error()); failed = true; }
                 while (!go.load()) {}
                 for (int i = 0; i < iters + 100 && !failed; i++)
                 {
@@ -50,6 +57,11 @@ int main(int argc, char** argv)
                     memset(job, 0, sizeof(*job));
                     job->log2CUSize = log2cu; job->log2TrMax = 5; job->log2TrMin = 5; job->chroma = 1; job->bitDepth = 8; job->quantOffset = 85; job->signHide = 1; job->reserved = stamps;
                     for (int p = 0; p < 3; p++) { job->qpRem[p] = 2; job->qpPer[p] = 5; job->quantScale[p] = 20560; job->dequantScale[p] = 51; }
+                    if (dn == 1)
+                    {
+                        job->coefMode = X265HIP_CUJOB_DENOISE;
+                        memcpy(offsets, tabs.data(), tabs.size() * sizeof(uint16_t));
+                    }
                     memcpy(pixels, src.data(), bytes);
                     uint32_t seq = 0;
                     if (x265hip_cuserve_submit(cs, t, &seq)) { fprintf(stderr, "submit: %s\n", x265hip_last_error()); failed = true; break; }
@@ -77,6 +89,13 @@ int main(int argc, char** argv)
                         }
                     }
                     volatile int16_t sink = levels[0] + resi[0]; (void)sink;
+                    if (dn == 1)
+                    {
+                        // what the binding does with the block: every entry of the units it answers is added to a sum
+                        uint32_t acc = 0;
+                        for (int k = 0; k < N * N + N * N / 2; k++) acc += absCoef[k];
+                        volatile uint32_t sink2 = acc; (void)sink2;
+                    }
                     const double t1 = now_us();
                     if (i >= 100) { lat[t].push_back(t1 - t0); first[t].push_back(tFirst); dev[t].push_back(units[0].fwdTicks * 0.01); }
                     if (i >= 100 && stamps)
@@ -95,7 +114,7 @@ int main(int argc, char** argv)
             go = 1;
             for (auto& x : th) x.join();
             const double wall = now_us() - w0;
-            if (failed) { printf("FAILED (mode %d, CU %d, %d threads)\n", mode, 1 << log2cu, T); x265hip_cuserve_close(cs); return 1; }
+            if (failed) { printf("FAILED (mode %d, CU %d, %d threads)\n", mode, 1 << log2cu, T); return false; }
             std::vector<double> all, f, dv;
             for (auto& v : lat) all.insert(all.end(), v.begin(), v.end());
             for (auto& v : first) f.insert(f.end(), v.begin(), v.end());
@@ -103,8 +122,9 @@ int main(int argc, char** argv)
             std::sort(dv.begin(), dv.end());
             std::sort(all.begin(), all.end()); std::sort(f.begin(), f.end());
             double sum = 0; for (double x : all) sum += x;
-            printf("%s, %dx%d CU (4:2:0, 8 bit, 32x32 transforms), %2d thread%s: whole job mean %6.1f us, median %6.1f, p99 %6.1f; first luma unit forward half median %6.1f us (%4.1f us of it on the device, doorbell seen -> ready word issued); %.0f jobs/s in total\n",
-                   mode ? "one launch per job" : "resident server   ", 1 << log2cu, 1 << log2cu, T, T > 1 ? "s" : " ", sum / all.size(), all[all.size() / 2],
+            printf("%s, %dx%d CU (4:2:0, 8 bit, 32x32 transforms%s), %2d thread%s: whole job mean %6.1f us, median %6.1f, p99 %6.1f; first luma unit forward half median %6.1f us (%4.1f us of it on the device, doorbell seen -> ready word issued); %.0f jobs/s in total\n",
+                   mode ? "one launch per job" : "resident server   ", 1 << log2cu, 1 << log2cu, dn == 1 ? ", DENOISE job" : dn == 2 ? ", plain job after the denoise call" : "", T, T > 1 ? "s" : " ",
+                   sum / all.size(), all[all.size() / 2],
                    all[(size_t)(all.size() * 0.99)], f[f.size() / 2], dv[dv.size() / 2], (double)T * (iters + 100) / (wall * 1e-6));
             if (stamps)
                 for (int w = 0; w < 2; w++)
@@ -121,6 +141,13 @@ int main(int argc, char** argv)
                            "inverse transform done %.2f, readyInv issued %.2f\n", w ? "first Cb  " : "first luma", med[0], med[1], med[2], med[3], med[4], med[5], med[6]);
                 }
             fflush(stdout);
+            return true;
+        };
+    for (int log2cu = 5; log2cu <= 6; log2cu++)
+        for (int T : { 1, 4, 16 })
+        {
+            if ((only && (only[0] != 'c' || only[2] != '0' + log2cu)) || (onlyT && T != onlyT)) continue;
+            if (!run_cu(log2cu, T, 0)) { x265hip_cuserve_close(cs); return 1; }
         }
     // ---- SAO statistics jobs (x265hip_saojob): a whole 64x64 CTU, three planes, every class; what SAO::calcSaoStatsCTU's seam hands over per CTU
     const int saoDepth = getenv("CUSERVE_RT_SAO_DEPTH") ? atoi(getenv("CUSERVE_RT_SAO_DEPTH")) : 8, saoPlanes = saoDepth > 8 ? 1 : 3, last = saoPlanes - 1;
@@ -250,6 +277,14 @@ int main(int argc, char** argv)
                mode ? "one launch per job" : "resident server   ", T, T > 1 ? "s" : " ", all[all.size() / 2], all[(size_t)(all.size() * 0.99)], dv[dv.size() / 2]);
         fflush(stdout);
     }
+    // ---- denoise jobs last: the first x265hip_cujob_denoise call has the service's kernels replaced (everything above ran on the kernels a service without
+    // noise reduction runs)
+    for (int dn : { 1, 2 })
+        for (int T : { 1, 4, 16 })
+        {
+            if ((only && only[0] != 'd') || (onlyT && T != onlyT)) continue;
+            if (!run_cu(5, T, dn)) { x265hip_cuserve_close(cs); return 1; }
+        }
     uint64_t jobs = 0, starts = 0, ns = 0;
     x265hip_cuserve_stats(cs, &jobs, &starts, &ns);
     printf("%llu jobs, %llu server starts, %.1f us of device time per job\n", (unsigned long long)jobs, (unsigned long long)starts, jobs ? ns * 1e-3 / jobs : 0.0);

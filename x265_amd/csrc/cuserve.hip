@@ -54,6 +54,7 @@ struct SlotIn
     uint32_t pad0[31];
     alignas(128) x265hip_cujob job;              // 80 bytes; the pixel block follows at +128 so that header and pixels are ONE run of 16-byte chunks
     alignas(128) unsigned char pixels[X265HIP_CUJOB_PIXEL_BYTES];
+    alignas(128) uint16_t offsets[X265HIP_CUJOB_DENOISE_ENTRIES];      // a denoise job's offset tables (x265hip_cujob_denoise): read by the lanes that use them, never staged
 };
 struct SlotOut
 {
@@ -62,6 +63,7 @@ struct SlotOut
     alignas(64) x265hip_cujob_unit units[X265HIP_CUJOB_MAX_UNITS];
     alignas(64) int16_t levels[kInts];
     alignas(64) int16_t resi[kInts];
+    alignas(64) uint16_t absCoef[kInts];         // a denoise job's |coefficient before denoise|, laid out like levels
 };
 
 // ---- up-right diagonal scans (6.5.3): position k of the scan of an n x n grid -> (x, y) ---------------------------------------------------------
@@ -152,7 +154,8 @@ static_assert(kSaoPixelBytes <= X265HIP_CUJOB_PIXEL_BYTES && (128 + kSaoPixelByt
 
 // qTab / dqTab: the unit's (size, plane, rem) matrices of the job's table set (x265hip_cujob::scaling), n * n int32 each, rows contiguous; null: the flat quantiser.
 // per: the plane's qpParam.per, which dequant_scaling takes apart from the matrix
-struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal, per; const int32_t* qTab; const int32_t* dqTab; };
+// nrTab: a denoise job's offset table of the unit's category (n * n uint16 of the slot's offset block, rows contiguous); null: no denoise
+struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal, per; const int32_t* qTab; const int32_t* dqTab; const uint16_t* nrTab; };
 
 // A table set in device memory: X265HIP_CUJOB_SCALING_ENTRIES quantiser entries, then as many dequantiser entries; [size 8, 16, 32][plane][rem][n * n]
 constexpr int kSetInts = 2 * X265HIP_CUJOB_SCALING_ENTRIES;
@@ -174,6 +177,20 @@ __device__ __forceinline__ void load_table4(const int32_t* p, int* v)
     const int4 q = *reinterpret_cast<const int4*>(p);
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
 }
+// denoiseDct_c (dct.cpp:744-755) of coefficients c[0 .. K - 1] with offsets packed two to a word (contiguous entries of the job's block, requested ahead of the
+// forward transform like a table set's): a[] = |c| — what the reference adds to residualSum — and c[] = the denoised coefficient
+template <int K>
+__device__ __forceinline__ void denoise(int* c, int* a, const uint32_t* packed)
+{
+#pragma unroll
+    for (int i = 0; i < K; i++)
+    {
+        const int off = (int)((packed[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+        a[i] = iabs(c[i]);
+        const int d = a[i] - off;
+        c[i] = d < 0 ? 0 : c[i] < 0 ? -d : d;
+    }
+}
 
 __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int plane, int log2n, const int32_t* sets)
 {
@@ -192,6 +209,7 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
     p.maxVal = (1 << depth) - 1;
     p.per = j.qpPer[plane];
     p.qTab = p.dqTab = nullptr;
+    p.nrTab = nullptr;
     if (j.scaling && sets)
     {
         // (x265hip_cuserve_submit has looked at the id and at rem: the offsets stay inside the set)
@@ -206,10 +224,13 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
 //   pw / N, twice that for a 4:2:2 chroma plane)
 // SC: the units are quantised and dequantised with the matrices qp.qTab / qp.dqTab (a lane's 16 coefficients are 16 contiguous int32 of the matrix: four
 // 16-byte loads, issued ahead of the stage in front of the one that needs them); the flat instantiation is the code it was
-template <typename P, int N, bool SC>
+// DN: the kernel serves denoise jobs (the *_sets pair): when the job is one (qp.nrTab, uniform over the workgroup), denoiseDct between the forward transform and
+// the quantiser with the offsets qp.nrTab (a lane's 16 are 32 contiguous bytes); |c| goes out in absCoef.  (One instantiation for both kinds of job: a kernel
+// that held the chains twice kept some of sign hiding's level arrays in scratch.)
+template <typename P, int N, bool SC, bool DN>
 __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64], const P* src, const P* prd, int pw, int u0, int count, const PlaneParams qp,
                                            bool signHide, x265hip_cujob_unit* units, int unitBase, int16_t* levels, int16_t* resi, int elemBase, uint32_t seq, uint64_t t0, bool stamps,
-                                           int coef)
+                                           int coef, [[maybe_unused]] uint16_t* absCoef)
 {
     // job.reserved != 0 (tools/micro/cuserve_rt): 100 MHz ticks since the doorbell was seen at six points of the chain, two per reserved word of the unit
     uint32_t stamp[6] = { 0, 0, 0, 0, 0, 0 };
@@ -233,6 +254,13 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
     {
 #pragma unroll
         for (int k = 0; k < 4; k++) load_table4(qp.qTab + ((lane * 16) % (N * N)) + 4 * k, qs + 4 * k);
+    }
+    [[maybe_unused]] uint32_t nr[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    [[maybe_unused]] const bool dn = DN && qp.nrTab != nullptr;
+    if constexpr (DN) if (dn)
+    {
+        const uint4 n0 = *reinterpret_cast<const uint4*>(qp.nrTab + ((lane * 16) % (N * N))), n1 = *reinterpret_cast<const uint4*>(qp.nrTab + ((lane * 16) % (N * N)) + 8);
+        nr[0] = n0.x; nr[1] = n0.y; nr[2] = n0.z; nr[3] = n0.w; nr[4] = n1.x; nr[5] = n1.y; nr[6] = n1.z; nr[7] = n1.w;
     }
     // ---- residual = source - prediction (two runs of 8 per lane; kept in registers for the distortions)
     int fv[16], pv[16];
@@ -265,6 +293,29 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
     __builtin_amdgcn_s_waitcnt(0xc07f);
     mfma_pass<N, false>(t.b, t.a, lane, bF, corrF, qp.s2f);
     __builtin_amdgcn_s_waitcnt(0xc07f);
+    if constexpr (DN)
+    {
+        // ---- denoiseDct of the residual's coefficients (not of the source block's transform): a lane's 16, in place; |c| out
+        if (dn && !srcOnly)
+        {
+            const int gD = (lane * 16) / (N * N);
+#pragma unroll
+            for (int half = 0; half < 2; half++)
+            {
+                const int e = lane * 16 + half * 8;
+                int cf[8], ab[8];
+                load4(t.a + e, cf); load4(t.a + e + 4, cf + 4);
+                denoise<8>(cf, ab, nr + 4 * half);
+                store4(t.a + e, cf); store4(t.a + e + 4, cf + 4);
+                if (gD < count)
+                {
+                    uint16_t* dstA = absCoef + elemBase + (u0 + gD) * N * N + (e % (N * N));
+                    store4(dstA, ab); store4(dstA + 4, ab + 4);
+                }
+            }
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+        }
+    }
     XH_STAMP(1);
     if (coef)
     {
@@ -720,9 +771,12 @@ __device__ __forceinline__ void team_inverse32(TileLds& t, TeamLds& tm, const P*
 }
 
 // unit `u` (raster order; `pw` elements per row of the plane in LDS) of a plane whose transform size is 32: tile_chain<P, 32>'s work for one unit
-template <typename P, bool SC>
+// DN: every thread denoises its four coefficients behind the forward transform; their |c| meet in `absLds` (a tile no team unit uses) and leave through wave 0
+// with the levels
+template <typename P, bool SC, bool DN>
 __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* src, const P* prd, int pw, int u, const PlaneParams qp, bool signHide,
-                                             x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef)
+                                             x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef,
+                                             [[maybe_unused]] uint16_t* absLds, [[maybe_unused]] uint16_t* absCoef)
 {
     uint32_t stamp[6] = { 0, 0, 0, 0, 0, 0 };
     XH_STAMP(0);
@@ -736,6 +790,13 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
     // (SC: the thread's four entries of the quantiser matrix, one 16-byte load that the forward transform hides)
     [[maybe_unused]] int qs[4], dqs[4];
     if constexpr (SC) load_table4(qp.qTab + e, qs);
+    [[maybe_unused]] uint32_t nr[2] = { 0, 0 };
+    [[maybe_unused]] const bool dn = DN && qp.nrTab != nullptr;
+    if constexpr (DN) if (dn)
+    {
+        const uint2 n0 = *reinterpret_cast<const uint2*>(qp.nrTab + e);
+        nr[0] = n0.x; nr[1] = n0.y;
+    }
     int fv[4], pv[4];
     {
         const int off = (uy * 32 + (e >> 5)) * pw + ux * 32 + (e & 31);
@@ -756,6 +817,20 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
     team_barrier();
     team_pass<false>(t.b, t.a, tid, oF, qp.s2f);
     team_barrier();
+    if constexpr (DN)
+    {
+        // ---- denoiseDct (tile_chain): a thread's own four coefficients, in place; the quantiser below reads the same four, so only coefficient mode — whose
+        // block wave 0 carries out — meets at a barrier behind it
+        if (dn && !srcOnly)
+        {
+            int cf[4], ab[4];
+            load4(t.a + e, cf);
+            denoise<4>(cf, ab, nr);
+            store4(t.a + e, cf);
+            store4(absLds + e, ab);
+            if (coef) team_barrier();
+        }
+    }
     XH_STAMP(1);
     if (coef)
     {
@@ -768,6 +843,15 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
             const uint4 c0 = *reinterpret_cast<const uint4*>(t.a + lane * 16), c1 = *reinterpret_cast<const uint4*>(t.a + lane * 16 + 8);
             *reinterpret_cast<uint4*>(dstC + lane * 16) = c0;
             *reinterpret_cast<uint4*>(dstC + lane * 16 + 8) = c1;
+            if constexpr (DN)
+            {
+                if (dn && !srcOnly)
+                {
+                    const uint4 a0 = *reinterpret_cast<const uint4*>(absLds + lane * 16), a1 = *reinterpret_cast<const uint4*>(absLds + lane * 16 + 8);
+                    *reinterpret_cast<uint4*>(absCoef + lane * 16) = a0;
+                    *reinterpret_cast<uint4*>(absCoef + lane * 16 + 8) = a1;
+                }
+            }
             if (lane == 0)
             {
                 if (srcOnly)
@@ -900,6 +984,7 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
     // ---- dequant_normal -> a (every thread its four); wave 0 takes the unit's levels into registers: they leave through ONE wave, whose release store of the ready
     // word then orders them (stores of another wave are not ordered against it by anything cheaper than a system-scope release fence per wave: profiles/r06_v1_team_fence.txt)
     uint4 keep0 = { 0, 0, 0, 0 }, keep1 = { 0, 0, 0, 0 };
+    [[maybe_unused]] uint4 keepA0 = { 0, 0, 0, 0 }, keepA1 = { 0, 0, 0, 0 };
     {
         int lv[4], dq[4];
         const int dqAdd = 1 << (qp.dqShift - 1);
@@ -915,6 +1000,12 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
         {
             keep0 = *reinterpret_cast<const uint4*>(t.b + lane * 16);
             keep1 = *reinterpret_cast<const uint4*>(t.b + lane * 16 + 8);
+            // (every thread's |c| is in absLds since the barrier behind the quantiser)
+            if constexpr (DN) if (dn)
+            {
+                keepA0 = *reinterpret_cast<const uint4*>(absLds + lane * 16);
+                keepA1 = *reinterpret_cast<const uint4*>(absLds + lane * 16 + 8);
+            }
         }
     }
     team_barrier();
@@ -923,6 +1014,11 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
     {
         *reinterpret_cast<uint4*>(levels + lane * 16) = keep0;
         *reinterpret_cast<uint4*>(levels + lane * 16 + 8) = keep1;
+        if constexpr (DN) if (dn)
+        {
+            *reinterpret_cast<uint4*>(absCoef + lane * 16) = keepA0;
+            *reinterpret_cast<uint4*>(absCoef + lane * 16 + 8) = keepA1;
+        }
         if (lane == 0)
         {
             un->numSig = (uint32_t)numSig;
@@ -1021,9 +1117,10 @@ __device__ __forceinline__ unsigned long long solo_total(uint32_t v)
            (uint32_t)__builtin_amdgcn_readlane((int)r, 32) + (uint32_t)__builtin_amdgcn_readlane((int)r, 48);
 }
 
-template <typename P, bool SC>
+template <typename P, bool SC, bool DN>
 __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)[64], const P* src, const P* prd, const PlaneParams qp, bool signHide,
-                                             x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef)
+                                             x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef,
+                                             [[maybe_unused]] uint16_t* absCoef)
 {
     uint32_t stamp[6] = { 0, 0, 0, 0, 0, 0 };
     XH_STAMP(0);
@@ -1032,6 +1129,13 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
     const TeamOperand& oI = op[1][lane];
     [[maybe_unused]] int qs[4], dqs[4];
     if constexpr (SC) load_table4(qp.qTab + e, qs);
+    [[maybe_unused]] uint32_t nr[2] = { 0, 0 };
+    [[maybe_unused]] const bool dn = DN && qp.nrTab != nullptr;
+    if constexpr (DN) if (dn)
+    {
+        const uint2 n0 = *reinterpret_cast<const uint2*>(qp.nrTab + e);
+        nr[0] = n0.x; nr[1] = n0.y;
+    }
     int fv[4], pv[4];
     {
         load4(src + e, fv);
@@ -1048,6 +1152,15 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
     // ---- forward transform: a -> b -> a
     solo_pass16<false>(t.a, t.b, lane, oF, qp.s1f);
     solo_pass16<false>(t.b, t.a, lane, oF, qp.s2f);
+    if constexpr (DN) if (dn)
+    {
+        // ---- denoiseDct (tile_chain): a lane's own four coefficients, in place; |c| out
+        int cf[4], ab[4];
+        load4(t.a + e, cf);
+        denoise<4>(cf, ab, nr);
+        store4(t.a + e, cf);
+        store4(absCoef + e, ab);
+    }
     XH_STAMP(1);
     if (coef)
     {
@@ -1319,8 +1432,9 @@ __device__ __forceinline__ void build_operands(JobLds& L)
 // other, because the submitting thread asks for them one after the other and waits for the first — role 1 the chroma units, a 32x32 tile per wave as before.
 // Every unit is written by exactly one workgroup and carries its own ready words, so the two never meet.
 // SC: the job names a table set and its units are quantised on the device (run_job)
-template <typename P, bool SC>
-__device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0, int role, bool team, const int32_t* sets)
+// DN: the kernel serves denoise jobs: a job that carries X265HIP_CUJOB_DENOISE finds its offset tables in the slot's input half at `nrBlock`
+template <typename P, bool SC, bool DN>
+__device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0, int role, bool team, const int32_t* sets, [[maybe_unused]] const uint16_t* nrBlock)
 {
     const int wv = threadIdx.x >> 6;
     const x265hip_cujob& j = L.job;
@@ -1330,7 +1444,10 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
     const int lumaElems = N * N, chromaElems = x265hipi_cujob_chroma_elems(j.chroma, lumaElems), planeElems = lumaElems + 2 * chromaElems;
     const P* src = reinterpret_cast<const P*>(L.pix);
     const P* prd = src + planeElems;
-    if (j.coefMode == X265HIP_CUJOB_INVERSE)
+    // (the flag is masked where it can be set: the other kernels are never given a job with it, x265hip_cuserve_submit)
+    const uint32_t coefMode = DN ? j.coefMode & ~X265HIP_CUJOB_DENOISE : j.coefMode;
+    [[maybe_unused]] const bool denoiseJob = DN && (j.coefMode & X265HIP_CUJOB_DENOISE) != 0;
+    if (coefMode == X265HIP_CUJOB_INVERSE)
     {
         if (role == 0) team_inverse_job<P, SC>(s, L, seq, t0, sets);
         return;
@@ -1352,9 +1469,10 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
             const P* ps = plane == 0 ? src : plane == 1 ? src + lumaElems : src + lumaElems + chromaElems;
             const P* pp = plane == 0 ? prd : plane == 1 ? prd + lumaElems : prd + lumaElems + chromaElems;
             const int pw = plane ? NC : N;
-            const PlaneParams qp = plane_params(j, plane, log2n, SC ? sets : nullptr);
+            PlaneParams qp = plane_params(j, plane, log2n, SC ? sets : nullptr);
+            if constexpr (DN) if (denoiseJob) qp.nrTab = nrBlock + x265hipi_cujob_denoise_offset(&j, sHi, sLo, sz, plane);
             // coefficient mode: a luma tile whose source block is wanted as well is TWO work items (residual part, source part)
-            const int parts = j.coefMode && j.sourceDct && plane == 0 ? 2 : 1;
+            const int parts = coefMode && j.sourceDct && plane == 0 ? 2 : 1;
             const int unitBase = x265hipi_cujob_unit_index(&j, sHi, sz, plane, 0, 0);
             const int elemBase = x265hipi_cujob_elem_offset(&j, sHi, sz, plane, 0, 0);
             if (plane == 0 && log2n == 5 && team)
@@ -1363,9 +1481,9 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
                 for (int u = 0; u < nUnits; u++)
                     for (int part = 0; part < parts; part++)
                     {
-                        const int coef = !j.coefMode ? 0 : parts == 1 ? 1 : part == 0 ? 1 | 4 : 2 | 4;
-                        team_chain32<P, SC>(L.tile[0], L.team, ps, pp, pw, u, qp, j.signHide != 0, s->units + unitBase + u, s->levels + elemBase + u * 1024,
-                                        s->resi + elemBase + u * 1024, seq, t0, j.reserved != 0, coef);
+                        const int coef = !coefMode ? 0 : parts == 1 ? 1 : part == 0 ? 1 | 4 : 2 | 4;
+                        team_chain32<P, SC, DN>(L.tile[0], L.team, ps, pp, pw, u, qp, j.signHide != 0, s->units + unitBase + u, s->levels + elemBase + u * 1024,
+                                        s->resi + elemBase + u * 1024, seq, t0, j.reserved != 0, coef, reinterpret_cast<uint16_t*>(L.tile[1].a), s->absCoef + elemBase + u * 1024);
                     }
                 continue;
             }
@@ -1373,14 +1491,14 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
             {
                 if ((tile & 3) != wv) continue;
                 const int k = kk / parts;
-                const int coef = !j.coefMode ? 0 : parts == 1 ? 1 : (kk % parts) == 0 ? 1 | 4 : 2 | 4;
+                const int coef = !coefMode ? 0 : parts == 1 ? 1 : (kk % parts) == 0 ? 1 | 4 : 2 | 4;
                 const int u0 = k * G, count = nUnits - u0 < G ? nUnits - u0 : G;
-                if (log2n == 5) tile_chain<P, 32, SC>(L.tile[wv], L.bop[2], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
+                if (log2n == 5) tile_chain<P, 32, SC, DN>(L.tile[wv], L.bop[2], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
                 else if (log2n == 4 && nUnits == 1 && plane && team)
                     // (the chroma units of a 32x32 CU: one 16x16 unit per plane, the wave's only work)
-                    solo_chain16<P, SC>(L.tile[wv], L.team.op16, ps, pp, qp, j.signHide != 0, s->units + unitBase, s->levels + elemBase, s->resi + elemBase, seq, t0, j.reserved != 0, coef);
-                else if (log2n == 4) tile_chain<P, 16, SC>(L.tile[wv], L.bop[1], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
-                else tile_chain<P, 8, SC>(L.tile[wv], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef);
+                    solo_chain16<P, SC, DN>(L.tile[wv], L.team.op16, ps, pp, qp, j.signHide != 0, s->units + unitBase, s->levels + elemBase, s->resi + elemBase, seq, t0, j.reserved != 0, coef, s->absCoef + elemBase);
+                else if (log2n == 4) tile_chain<P, 16, SC, DN>(L.tile[wv], L.bop[1], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
+                else tile_chain<P, 8, SC, DN>(L.tile[wv], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
             }
         }
     }
@@ -1696,7 +1814,8 @@ __device__ __forceinline__ void run_intra(SlotOut* s, JobLds& L, uint32_t seq, u
 
 // one job: `ticket` says how many bytes the job holds, so header and pixels arrive in one round trip.  role 0 / 1: this workgroup's half of a CU job (luma /
 // chroma: each fetches the header and its own planes only); SAO statistics and intra scans are role 0's alone
-// SETS: the kernel was started for a service with table sets (cu_server_kernel_sets / cu_job_kernel_sets) and holds the SC instantiations beside the flat ones
+// SETS: the kernel was started for a service with table sets or denoise jobs (cu_server_kernel_sets / cu_job_kernel_sets) and holds the SC and DN instantiations
+// beside the flat ones
 template <bool SETS>
 __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L, uint32_t ticket, uint64_t* busyTicks, int role, bool team, const int32_t* sets)
 {
@@ -1749,12 +1868,14 @@ __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L
         }
         else if constexpr (SETS)
         {
-            if (ticket & 8) run_tiles<uint16_t, true>(s, L, ticket, t0, role, team, sets);
-            else run_tiles<uint8_t, true>(s, L, ticket, t0, role, team, sets);
+            if (ticket & 8) run_tiles<uint16_t, true, true>(s, L, ticket, t0, role, team, sets, sin->offsets);
+            else run_tiles<uint8_t, true, true>(s, L, ticket, t0, role, team, sets, sin->offsets);
         }
     }
-    else if (ticket & 8) run_tiles<uint16_t, false>(s, L, ticket, t0, role, team, nullptr);
-    else run_tiles<uint8_t, false>(s, L, ticket, t0, role, team, nullptr);
+    // (X265HIP_CUJOB_DENOISE is in the header, which is known by now, and only the kernels that were started for such jobs look at it: x265hip_cuserve_submit
+    // refuses the flag on a service that has not been switched over, x265hip_cujob_denoise.  The offset block is read by the lanes that use it.)
+    else if (ticket & 8) run_tiles<uint16_t, false, SETS>(s, L, ticket, t0, role, team, nullptr, SETS ? sin->offsets : nullptr);
+    else run_tiles<uint8_t, false, SETS>(s, L, ticket, t0, role, team, nullptr, SETS ? sin->offsets : nullptr);
     __syncthreads();
     if (tid == 0)
         *busyTicks += wall_clock64() - t0;
@@ -1918,6 +2039,7 @@ struct x265hip_cuserve
     int32_t* sets = nullptr;                      // device memory: X265HIP_CUJOB_SCALING_SETS table sets of kSetInts int32 (x265hip_cujob_scaling_add; allocated with the first)
     std::atomic<uint32_t> nsets{ 0 };             // sets registered: ids 1 .. nsets are valid in x265hip_cujob::scaling
     std::mutex setLock;
+    std::atomic<bool> denoise{ false };           // x265hip_cujob_denoise was called: the *_sets kernels serve (they hold the denoise step), jobs may carry the flag
     uint64_t idleUs = 2000;
 };
 static std::mutex g_openLock;
@@ -1948,7 +2070,7 @@ static int start_server(x265hip_cuserve* cs)
     if (e == hipSuccess)
     {
         const uint64_t idle = cs->idleUs * 100 | (getenv("X265HIP_CUSERVE_SPIN") && atoi(getenv("X265HIP_CUSERVE_SPIN")) ? 1ull << 63 : 0ull) | (team_off() ? 1ull << 62 : 0ull);
-        if (cs->sets)
+        if (cs->sets || cs->denoise.load(std::memory_order_acquire))
             hipLaunchKernelGGL(cu_server_kernel_sets, dim3(2 * cs->slots), dim3(256), 0, cs->serverStream, cs->inDev, cs->outDev, cs->devHostCtl, cs->ctl, gen ? gen : 1u, idle,
                                (const int32_t*)cs->sets);
         else
@@ -2188,6 +2310,14 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
     if (j.log2CUSize < 4 || j.log2CUSize > 6 || x265hipi_cujob_levels(&j, &sHi, &sLo) < 1 || !valid_depth((int)j.bitDepth) || j.chroma > 3)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: CU 2^%u, transform sizes 2^%u..2^%u, depth %u, chroma format %u", j.log2CUSize, j.log2TrMin, j.log2TrMax,
                          j.bitDepth, j.chroma);
+    // the mode word: coefficient mode or not, with or without denoise, or an inverse job (which has nothing to denoise); denoise only on a service whose
+    // kernels hold the step (x265hip_cujob_denoise)
+    const uint32_t plainMode = j.coefMode & ~X265HIP_CUJOB_DENOISE;
+    const bool denoiseJob = (j.coefMode & X265HIP_CUJOB_DENOISE) != 0;
+    if (plainMode > 1 && !(j.coefMode == X265HIP_CUJOB_INVERSE))
+        return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: coefMode %u", j.coefMode);
+    if (denoiseJob && !cs->denoise.load(std::memory_order_acquire))
+        return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: a denoise job on a service that x265hip_cujob_denoise was never called on");
     // a table set: one that is registered, and quantiser parameters that stay inside its matrices (rem picks the matrix, per is a shift count)
     if (j.scaling)
     {
@@ -2206,7 +2336,7 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: an inverse job is one 32x32 luma unit (CU 2^%u, chroma %u, transform 2^%d)", j.log2CUSize, j.chroma, sHi);
     // (bit 7: the device quantises or dequantises with a table set — not in coefficient mode, where the id is carried unused)
     const uint32_t seq = (run << 8) | (j.log2CUSize - 4) | (j.chroma ? 4u | ((j.chroma - 1) << 5) : 0u) | (j.bitDepth > 8 ? 8u : 0u) | (inverseJob ? 16u : 0u) |
-                         (j.scaling && (!j.coefMode || inverseJob) ? 128u : 0u);
+                         (j.scaling && (!plainMode || inverseJob) ? 128u : 0u);
     *seqOut = seq;
     cs->jobs.fetch_add(1, std::memory_order_relaxed);
     {
@@ -2222,7 +2352,7 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
         int cur = -1;
         (void)hipGetDevice(&cur);
         if (cur != cs->device) (void)hipSetDevice(cs->device);
-        if (cs->sets)
+        if (cs->sets || cs->denoise.load(std::memory_order_acquire))
             hipLaunchKernelGGL(cu_job_kernel_sets, dim3(2), dim3(256), 0, cs->jobStreams[slot], cs->inDev + slot, cs->outDev + slot, seq, &cs->ctl->busyTicks[2 * slot],
                                team_off() ? 0u : 1u, (const int32_t*)cs->sets);
         else
@@ -2246,7 +2376,37 @@ uint32_t x265hip_cujob_formats(void)
 
 uint32_t x265hip_cujob_features(void)
 {
-    return 1u;                                                                               // bit 0: table sets of scaling lists (x265hip_cujob::scaling)
+    return 1u | 2u;                                                                          // bit 0: table sets of scaling lists (x265hip_cujob::scaling); bit 1: X265HIP_CUJOB_DENOISE
+}
+
+int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef)
+{
+    if (!cs || slot < 0 || slot >= cs->slots) return set_error(X265HIP_EINVAL, "x265hip_cujob_denoise: slot %d", slot);
+    if (!cs->denoise.load(std::memory_order_acquire))
+    {
+        // once per service: the kernels that hold the denoise step take over.  A resident server leaves (jobs in progress are finished, waiters see
+        // x265hip_cuserve_poke == 1) and whoever submits next starts the other kernel — the pause of x265hip_cujob_scaling_add, without a copy
+        std::lock_guard<std::mutex> g(cs->setLock);
+        if (!cs->denoise.load())
+        {
+            servers_pause();
+            int e = X265HIP_OK;
+            if (cs->mode == 0)
+            {
+                const auto t0 = std::chrono::steady_clock::now();
+                while (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(10))
+                    __builtin_ia32_pause();
+                if (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0)
+                    e = set_error(X265HIP_EHIP, "x265hip_cujob_denoise: the resident server did not leave");
+            }
+            if (!e) cs->denoise.store(true, std::memory_order_release);
+            servers_resume();
+            if (e) return e;
+        }
+    }
+    if (offsets) *offsets = cs->in[slot].offsets;
+    if (absCoef) *absCoef = cs->out[slot].absCoef;
+    return X265HIP_OK;
 }
 
 int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id)

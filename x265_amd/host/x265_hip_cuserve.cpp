@@ -13,8 +13,10 @@
 // (a mailbox slot in page-locked memory; x265_amd/csrc/cuserve.hip), and while the reference's own estimateResidualQT body runs on this
 // thread, Quant::transformNxN / ::invtransformNxN called for a residual block of that CU copy the device's result instead of computing it.
 // Same values either way (tests/test_cuserve.py pins the device against the oracle's restatement of those two functions, which is pinned
-// against the reference's); anything the job does not cover (transform skip, transquant bypass, noise reduction, a scaling list with an entry below 8)
-// runs the reference's functions as before.  An encode with scaling lists hands its quantiser and dequantiser matrices to the service once, as a table set
+// against the reference's); anything the job does not cover (transform skip, transquant bypass, emergency denoise, a scaling list with an entry below 8)
+// runs the reference's functions as before.  Noise reduction (--nr-inter / --nr-intra; with X265HIP_CUSERVE_DENOISE=1, see g_denoise): the job carries the frame encoder's offset tables of its categories and
+// the flag X265HIP_CUJOB_DENOISE, the device denoises between transform and quantiser and returns |coefficient|, which the answering transformNxN adds to the
+// calling thread's residualSum exactly as the reference's body would have (denoise_sums below).  An encode with scaling lists hands its quantiser and dequantiser matrices to the service once, as a table set
 // (scaling_id below), and its jobs name the set.  Every chroma format is served (x265hip_cujob::chroma = the encoder's csp): a 4:2:2 chroma plane is N/2 x N with
 // the reference's two square sub-TUs per transform unit (search.cpp:3388-3393) as two rows of job units, a 4:4:4 one N x N with units of the luma size.
 //
@@ -49,6 +51,10 @@ int g_invJobs = X265_DEPTH == 8 ? 1 : 0;
 int g_rdoqJobs = 1;              // X265HIP_CUSERVE_RDOQ=0: CUs quantised by Quant::rdoQuant are not handed over (round 4's behaviour).  On: measured on the MI355X box at
                                  // BASELINE configs[2] / configs[3] (profiles/r05_v1_configs*_ab.txt): +2 % / +6 % fps, -3 % / -6 % CPU seconds
 int g_scaling = 1;               // X265HIP_CUSERVE_SCALING=0: CUs of an encode with scaling lists are not handed over (what the binding did before table sets existed)
+int g_denoise = 0;               // X265HIP_CUSERVE_DENOISE=1: CUs of an encode with noise reduction are handed over with their offset tables.  Off by default: measured on the
+                                 // MI355X box, 1080p preset medium --nr-inter 400 at the bench's thread arguments, 4 interleaved rounds, byte-identical (profiles/r08_v1_cujob_denoise_ab.txt):
+                                 // 8 bit 40.2 against 38.3 fps (25.7 against 27.6 CPU-s), Main10 34.2 against 32.0 (29.4 against 32.5 CPU-s) — ahead in the mean of both, but by
+                                 // less than the off leg's own rounds span (37.1-40.4, 30.6-33.5), which is the bar for a default
 int g_formats = 1;               // X265HIP_CUSERVE_FORMATS=0: CUs of 4:2:2 / 4:4:4 pictures are not handed over (what the binding did before their jobs existed)
 int g_slots = 64;                // X265HIP_CUSERVE_SLOTS: jobs that can be in flight (default: twice the CPUs this process may use, 16..64)
 bool g_verify = false;           // X265HIP_VERIFY=1: every served unit is recomputed by the reference's function and compared
@@ -63,7 +69,7 @@ std::atomic<bool> g_dead(false); // the device failed once: every later CU is co
 std::atomic<uint64_t> g_cycles[18][2], g_calls[18][2];
 __attribute__((tls_model("initial-exec"))) thread_local int t_inRqt = 0;
 
-struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs, scalingJobs, scalingKept; };
+struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs, scalingJobs, scalingKept, denoiseJobs, denoiseKept; };
 Counters g_count[64];
 std::atomic<int> g_nextShard(0);
 __attribute__((tls_model("initial-exec"))) thread_local int t_shard = -1;
@@ -103,6 +109,8 @@ struct Job
     // X265HIP_CUJOB_INVERSE), submitted when Quant::rdoQuant has made the unit's levels and collected by Quant::invtransformNxN (the tree codes the levels'
     // bits in between, search.cpp:3243-3262)
     struct InvAhead { bool active; int unit; Service* svc; int slot; uint32_t seq; const x265hip_cujob_unit* units; const int16_t* resi; int16_t sent[1024]; } inv;
+    NoiseReduction* nr;                  // a denoise job: the tables its offsets were copied from (an adopted job must be this scope's), and where its sums go
+    const uint16_t* absCoef;
     uint32_t seq;
     int slot;
     Service* svc;
@@ -226,6 +234,13 @@ void report()
             fprintf(stderr, "x265hip: cuserve: scaling lists: %d sets registered, %llu jobs carried one, %llu CUs kept on the host because of their list\n", scaling_sets(),
                     (unsigned long long)sj, (unsigned long long)sk2);
     }
+    {
+        uint64_t dj = 0, dk = 0;
+        for (int i = 0; i < 64; i++) { dj += g_count[i].denoiseJobs; dk += g_count[i].denoiseKept; }
+        if (dj || dk)
+            fprintf(stderr, "x265hip: cuserve: noise reduction: %llu jobs carried offsets, %llu CUs kept on the host because of their tables\n", (unsigned long long)dj,
+                    (unsigned long long)dk);
+    }
     if (dsb || dad)
         fprintf(stderr, "x265hip: cuserve: %llu sub_ps and %llu add_ps calls of those CUs put off because only the job's answers read their results (%llu + %llu run after all)\n",
                 (unsigned long long)dsb, (unsigned long long)dad, (unsigned long long)lsb, (unsigned long long)lad);
@@ -250,6 +265,7 @@ bool decide()
         if (getenv("X265HIP_CUSERVE_RDOQ")) g_rdoqJobs = atoi(getenv("X265HIP_CUSERVE_RDOQ")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_INVERSE")) g_invJobs = atoi(getenv("X265HIP_CUSERVE_INVERSE")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_FORMATS")) g_formats = atoi(getenv("X265HIP_CUSERVE_FORMATS")) ? 1 : 0;
+        if (getenv("X265HIP_CUSERVE_DENOISE")) g_denoise = atoi(getenv("X265HIP_CUSERVE_DENOISE")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_SCALING")) g_scaling = atoi(getenv("X265HIP_CUSERVE_SCALING")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_TIMEOUT_MS") && atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) > 0) g_timeoutNs = atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) * 1000000ll;
         if (getenv("X265HIP_CUSERVE_SLOTS")) g_slots = atoi(getenv("X265HIP_CUSERVE_SLOTS"));
@@ -320,7 +336,10 @@ bool service()
         const int e = places ? x265hip_cuserve_open_at(k, g_slots, g_mode, &sv.cs) : x265hip_cuserve_open(g_slots, g_mode, &sv.cs);
         bool ok = !e;
         for (int s = 0; ok && s < g_slots; s++)
+        {
             ok = !x265hip_cuserve_slot(sv.cs, s, &sv.mem[s].job, &sv.mem[s].pixels, &sv.mem[s].units, &sv.mem[s].levels, &sv.mem[s].resi);
+            sv.mem[s].nrOffsets = NULL; sv.mem[s].absCoef = NULL;
+        }
         if (!ok)
         {
             for (int j = 0; j <= k; j++)
@@ -482,6 +501,7 @@ __attribute__((tls_model("initial-exec"))) thread_local const ScalingList* t_lis
 __attribute__((tls_model("initial-exec"))) thread_local uint64_t t_listEpoch = 0;
 __attribute__((tls_model("initial-exec"))) thread_local uint32_t t_listId = 0;
 __attribute__((tls_model("initial-exec"))) thread_local bool t_listKept = false;      // the last make_header refused its CU because of the list
+__attribute__((tls_model("initial-exec"))) thread_local bool t_nrKept = false;        // ... because its denoise tables are not the frame encoder's own
 
 uint32_t scaling_lookup(const ScalingList* sl)
 {
@@ -561,10 +581,24 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
     const bool codeChroma = csp != X265_CSP_I400 && se->m_frame->m_fencPic->m_picCsp != X265_CSP_I400;
     // RDOQ (presets slow / slower): the quantiser is Quant::rdoQuant and stays on the host (its decisions read the entropy coder's state); the job carries
     // the transforms in front of it — coefficient mode (X265HIP_CUSERVE_RDOQ=0 switches it off)
-    t_listKept = false;
-    if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || (q.m_nr && q.m_nr->offset) || csp < X265_CSP_I400 || csp > X265_CSP_I444 ||
-        (csp != X265_CSP_I400) != codeChroma)
+    t_listKept = t_nrKept = false;
+    if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || csp < X265_CSP_I400 || csp > X265_CSP_I444 || (csp != X265_CSP_I400) != codeChroma)
         return false;
+    // noise reduction (quant.cpp:444-451): the job carries the offsets and the flag — for a library that has the denoise step (an older one, or the emulated one
+    // of the tests, does not: these CUs then stay on the host, as they do unless X265HIP_CUSERVE_DENOISE=1), and for the frame encoder's own tables only.  Under
+    // VBV emergency (frameencoder.cpp:576-583) `offset` points at the encoder-wide emergency tables and `residualSum` at one array all threads add to: the
+    // reference's business
+    const bool denoise = q.m_nr && q.m_nr->offset;
+    if (denoise)
+    {
+        if (!g_denoise || !x265hip_cujob_features || !x265hip_cujob_denoise || !(x265hip_cujob_features() & 2))
+            return false;
+        if (q.m_nr->offset != q.m_nr->nrOffsetDenoise || q.m_nr->residualSum != q.m_nr->nrResidualSum || q.m_nr->count != q.m_nr->nrCount)
+        {
+            t_nrKept = true;
+            return false;
+        }
+    }
     // 4:2:2 / 4:4:4: only a library that says it takes such jobs gets them (an older one, or the emulated one of the tests, has no x265hip_cujob_formats: these
     // CUs then stay on the host, as they do with X265HIP_CUSERVE_FORMATS=0)
     if (csp > X265_CSP_I420 && (!g_formats || !x265hip_cujob_formats || !((x265hip_cujob_formats() >> csp) & 1)))
@@ -591,7 +625,7 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
         hdr.quantScale[p] = q.m_scalingList->m_quantCoef[3][3 + p][qp.rem][0];          // flat: every entry of every size and list is s_quantScales[rem]
         hdr.dequantScale[p] = ScalingList::s_invQuantScales[qp.rem];
     }
-    hdr.coefMode = q.m_rdoqLevel ? 1 : 0;
+    hdr.coefMode = (q.m_rdoqLevel ? 1u : 0u) | (denoise ? X265HIP_CUJOB_DENOISE : 0u);
     hdr.sourceDct = q.m_rdoqLevel && q.m_psyRdoqScale ? 1 : 0;
     return true;
 }
@@ -693,7 +727,32 @@ bool submit(Search* se, Mode& mode, uint32_t log2CUSize, ShortYuv& resiYuv, cons
     const int slot = take_slot(&svc);
     if (slot < 0)
         return false;
-    const SlotMem& mem = svc->mem[slot];
+    SlotMem& mem = svc->mem[slot];
+    if (hdr.coefMode & X265HIP_CUJOB_DENOISE)
+    {
+        // (the slot is this thread's until it gives it back: its two blocks are asked for by whoever needs them first; the first call on a service has the
+        // kernels with the denoise step take over)
+        if (!mem.nrOffsets && x265hip_cujob_denoise(svc->cs, slot, &mem.nrOffsets, &mem.absCoef))
+        {
+            mem.nrOffsets = NULL;
+            give_slot(svc, slot);
+            device_failed("x265hip_cujob_denoise");
+            return false;
+        }
+        // the offset tables of the job's categories, cat = (log2n - 2) + 4 * (plane != 0) + 8 (inter), in the order of x265hipi_cujob_denoise_offset: packed
+        // here, then one front-to-back copy into the mailbox, like the pixels and in front of the same doorbell
+        alignas(64) uint16_t tabs[X265HIP_CUJOB_DENOISE_ENTRIES];
+        uint16_t* at = tabs;
+        const int hs = x265hipi_cujob_hshift(hdr.chroma);
+        for (int plane = 0; plane < (hdr.chroma ? 2 : 1); plane++)
+            for (int s = sHi; s >= sLo; s--)
+            {
+                const int log2n = plane ? s - hs : s;
+                memcpy(at, q.m_nr->offset[(log2n - 2) + 4 * plane + 8], sizeof(uint16_t) << (2 * log2n));
+                at += 1 << (2 * log2n);
+            }
+        memcpy(mem.nrOffsets, tabs, (size_t)(at - tabs) * sizeof(uint16_t));
+    }
     const int N = 1 << log2CUSize;
     const Yuv* fenc = mode.fencYuv;
     const Yuv* pred = &mode.predYuv;
@@ -738,10 +797,12 @@ bool submit(Search* se, Mode& mode, uint32_t log2CUSize, ShortYuv& resiYuv, cons
     inv_drop(j);
     j.log2CU = log2CUSize; j.sHi = sHi; j.sLo = sLo; j.slot = slot; j.svc = svc;
     j.job = mem.job; j.units = mem.units; j.levels = mem.levels; j.resiOut = mem.resi;
+    j.nr = (hdr.coefMode & X265HIP_CUJOB_DENOISE) ? q.m_nr : NULL; j.absCoef = mem.absCoef;
     j.active = true;
     counters().jobs.fetch_add(1, std::memory_order_relaxed);
     if (hdr.chroma > 1) counters().formatJobs.fetch_add(1, std::memory_order_relaxed);
     if (hdr.scaling) counters().scalingJobs.fetch_add(1, std::memory_order_relaxed);
+    if (j.nr) counters().denoiseJobs.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -1068,6 +1129,52 @@ inline void psy_ahead(Job& j, int u, int plane, int x, int y, int n)
     counters().psyAhead.fetch_add(1, std::memory_order_relaxed);
 }
 
+// ---- noise reduction: the side effect of a served Quant::transformNxN ---------------------------------------------------------------------------------------
+// The reference's body adds |coefficient| of every call to m_nr->residualSum[cat] and counts the call (quant.cpp:444-451, dct.cpp:751); the sums of a frame become
+// the next frame's offsets (frameencoder.cpp:1125-1152, :2098-2125), so they decide later bytes.  A call answered from a denoise job adds the job's absCoef block
+// instead — exactly once per answered call: a unit the device computed and the tree never asked for adds nothing, and every path that ends in the reference's
+// body (a miss, a failed wait, transform skip) adds nothing here because the body does.  Integer adds commute: the order among the calls does not matter.
+inline void denoise_sums(const Job& j, NoiseReduction* nr, uint32_t log2TrSize, TextType ttype, int eo)
+{
+    if (!(j.hdr.coefMode & X265HIP_CUJOB_DENOISE))
+        return;
+    const int cat = (int)(log2TrSize - 2) + 4 * (ttype != TEXT_LUMA) + 8, n2 = 1 << (2 * log2TrSize);
+    uint32_t* sum = nr->residualSum[cat];
+    const uint16_t* a = j.absCoef + eo;
+    for (int i = 0; i < n2; i++)
+        sum[i] += a[i];
+    nr->count[cat]++;
+}
+// X265HIP_VERIFY: the reference's body runs as well and adds the sums itself; what it added must be the job's absCoef block, and it counted one call
+struct DenoiseCheck
+{
+    bool on;
+    NoiseReduction* nr;
+    int cat, n2;
+    uint32_t count;
+    uint32_t before[1024];
+    DenoiseCheck(const Job& j, NoiseReduction* n, uint32_t log2TrSize, TextType ttype)
+        : on((j.hdr.coefMode & X265HIP_CUJOB_DENOISE) != 0), nr(n), cat((int)(log2TrSize - 2) + 4 * (ttype != TEXT_LUMA) + 8), n2(1 << (2 * log2TrSize)), count(0)
+    {
+        if (!on) return;
+        memcpy(before, nr->residualSum[cat], sizeof(uint32_t) * n2);
+        count = nr->count[cat];
+    }
+    void check(const Job& j, int eo) const
+    {
+        if (!on) return;
+        const uint32_t* sum = nr->residualSum[cat];
+        bool same = nr->count[cat] == count + 1;
+        for (int i = 0; i < n2 && same; i++)
+            same = sum[i] - before[i] == j.absCoef[eo + i];
+        if (!same)
+        {
+            fprintf(stderr, "x265hip: cuserve: VERIFY FAILED denoise category %d: what the reference added to residualSum is not the job's absCoef block\n", cat);
+            abort();
+        }
+    }
+};
+
 } // namespace
 
 // called by setupAssemblyPrimitives in the default table mode, after the psy lookups of x265_hip_srcplanes.cpp are in the table
@@ -1236,7 +1343,8 @@ bool adopt(Search* se, Mode& mode, const CUGeom& cuGeom)
     mode.cu.getInterTUQtDepthRange(range, 0);
     x265hip_cujob hdr;
     if (j.search != se || j.fencYuv != mode.fencYuv || j.log2CU != cuGeom.log2CUSize || j.resi[0] != se->m_rqt[cuGeom.depth].tmpResiYuv.m_buf[0] ||
-        !make_header(se, mode, cuGeom.log2CUSize, range, hdr) || memcmp(&hdr, &j.hdr, sizeof(hdr)))
+        !make_header(se, mode, cuGeom.log2CUSize, range, hdr) || memcmp(&hdr, &j.hdr, sizeof(hdr)) ||
+        ((hdr.coefMode & X265HIP_CUJOB_DENOISE) && j.nr != se->m_quant.m_nr))          // (the flag is part of the header; the tables are the same frame encoder's)
         return false;
     const Yuv& pred = mode.predYuv;
     const Yuv& fenc = *mode.fencYuv;
@@ -1342,6 +1450,7 @@ void Search::encodeResAndCalcRdInterCU(Mode& interMode, const CUGeom& cuGeom)
         {
             counters().skipped.fetch_add(1, std::memory_order_relaxed);
             if (t_listKept) counters().scalingKept.fetch_add(1, std::memory_order_relaxed);
+            if (t_nrKept) counters().denoiseKept.fetch_add(1, std::memory_order_relaxed);
         }
         else
             t_job.inTree = false;
@@ -1382,7 +1491,7 @@ uint32_t Quant::transformNxN(const CUData& cu, const pixel* fenc, uint32_t fencS
                     }
                 }
             }
-            if (j.hdr.coefMode)
+            if (j.hdr.coefMode & 1)
             {
                 // RDOQ: the device has transformed (residual -> m_resiDctCoeff, and for psy-rdoq source -> m_fencDctCoeff: quant.cpp:432, :436-442); the
                 // quantiser is the reference's own, called as Quant::transformNxN calls it (:454-455)
@@ -1400,7 +1509,9 @@ uint32_t Quant::transformNxN(const CUData& cu, const pixel* fenc, uint32_t fencS
                     memcpy(gotR, m_resiDctCoeff, sizeof(int16_t) * n2);
                     if (usePsy) memcpy(gotF, m_fencDctCoeff, sizeof(int16_t) * n2);
                     coeff_t want[1024];
+                    DenoiseCheck dn(j, m_nr, log2TrSize, ttype);
                     const uint32_t ns = refTransformNxN(this, cu, fenc, fencStride, residual, resiStride, want, log2TrSize, ttype, absPartIdx, useTransformSkip);
+                    dn.check(j, eo);
                     if (memcmp(gotR, m_resiDctCoeff, sizeof(int16_t) * n2) || (usePsy && memcmp(gotF, m_fencDctCoeff, sizeof(int16_t) * n2)))
                     {
                         fprintf(stderr, "x265hip: cuserve: VERIFY FAILED transformNxN (RDOQ) %dx%d plane %d: the device's transform coefficients differ from cu[].dct's\n",
@@ -1417,6 +1528,7 @@ uint32_t Quant::transformNxN(const CUData& cu, const pixel* fenc, uint32_t fencS
                     }
                     return numSigV;
                 }
+                denoise_sums(j, m_nr, log2TrSize, ttype, eo);
                 const uint32_t numSigQ = (this->*rdoQuant_func[log2TrSize - 2])(cu, coeff, ttype, absPartIdx, usePsy);
                 counters().fwd.fetch_add(1, std::memory_order_relaxed);
                 // the levels exist now; the tree codes their bits (search.cpp:3243-3262) and then asks for the unit's inverse: that half leaves here
@@ -1448,7 +1560,9 @@ uint32_t Quant::transformNxN(const CUData& cu, const pixel* fenc, uint32_t fencS
                 if (g_verify)
                 {
                     coeff_t want[1024];
+                    DenoiseCheck dn(j, m_nr, log2TrSize, ttype);
                     const uint32_t ns = refTransformNxN(this, cu, fenc, fencStride, residual, resiStride, want, log2TrSize, ttype, absPartIdx, useTransformSkip);
+                    dn.check(j, eo);
                     if (ns != numSig || memcmp(want, coeff, sizeof(coeff_t) * n2))
                     {
                         fprintf(stderr, "x265hip: cuserve: VERIFY FAILED transformNxN %dx%d plane %d: numSig %u (device) vs %u\n", 1 << log2TrSize, 1 << log2TrSize, (int)ttype,
@@ -1456,6 +1570,8 @@ uint32_t Quant::transformNxN(const CUData& cu, const pixel* fenc, uint32_t fencS
                         abort();
                     }
                 }
+                else
+                    denoise_sums(j, m_nr, log2TrSize, ttype, eo);
                 counters().fwd.fetch_add(1, std::memory_order_relaxed);
                 t_lastServedCoeff = coeff;
                 if (g_time)
@@ -1520,7 +1636,7 @@ void Quant::invtransformNxN(const CUData& cu, int16_t* residual, uint32_t resiSt
         }
         if (a.active) inv_drop(j);
     }
-    if (j.active && j.inTree && j.quant == this && !useTransformSkip && !bIntra && !j.hdr.coefMode)
+    if (j.active && j.inTree && j.quant == this && !useTransformSkip && !bIntra && !(j.hdr.coefMode & 1))
     {
         // which unit?  the one of this size and plane whose levels these are: equal levels have equal inverse transforms, so the comparison — not
         // any bookkeeping — is what makes the copy exact.  The tree asks for a unit's inverse right after its forward transform: look there first.

@@ -39,6 +39,8 @@ extern "C" uint32_t x265hip_cujob_formats(void) __attribute__((weak));
 // likewise: absent (or bit 0 clear) = no table sets, CUs of an encode with scaling lists stay on the host
 extern "C" uint32_t x265hip_cujob_features(void) __attribute__((weak));
 extern "C" int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id) __attribute__((weak));
+// likewise: absent (or bit 1 of the features clear) = no denoise jobs, CUs of an encode with noise reduction stay on the host
+extern "C" int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef) __attribute__((weak));
 
 namespace X265_NS {
 
@@ -71,7 +73,11 @@ extern void refCalcSaoStatsCTU(SAO* self, int addr, int plane) asm("_ZN4x2656SAO
 
 namespace cusvc {
 
-struct SlotMem { x265hip_cujob* job; void* pixels; const x265hip_cujob_unit* units; const int16_t* levels; const int16_t* resi; };
+struct SlotMem
+{
+    x265hip_cujob* job; void* pixels; const x265hip_cujob_unit* units; const int16_t* levels; const int16_t* resi;
+    uint16_t* nrOffsets; const uint16_t* absCoef;        // x265hip_cujob_denoise's blocks: asked for by the first denoise job that takes the slot (NULL before)
+};
 // one job service per place (X265HIP_DEVICES; one on the calling thread's device when no places are configured): every GPU of the encoder serves CU jobs
 struct Service
 {
