@@ -32,13 +32,15 @@ VALU_SAD_CEILING_T = 95.2     # T absolute differences per second: v_qsad_pk_u16
 EMITTED_PER_CTU = 16 * (512 + 4) + 4 * (1024 + 4) + (1024 + 4)     # 16x16 level: u16 entries; 32x32 and 64x64: u32; 4 bytes of origin per block
 
 
-def unit_bytes(S):
-    """SURVEY 8d unique footprint of the staged unit (one CTU) + what it emits"""
+def unit_bytes(S, depth=8):
+    """SURVEY 8d unique footprint of the staged unit (one CTU) + what it emits (16-bit pictures: two bytes per sample, every entry u32)"""
     R = 2 * S
+    if depth > 8:
+        return 2 * (64 * 64 + (64 + R - 1) ** 2) + 21 * (1024 + 4)
     return 64 * 64 + (64 + R - 1) ** 2 + EMITTED_PER_CTU
 
 
-def pictures(w, h, k, seed):
+def pictures(w, h, k, seed, depth=8):
     from x265_amd.synth import make_scene
     sc = make_scene(w, h, 8, seed=seed)
     ref = sc["ref"]
@@ -47,25 +49,35 @@ def pictures(w, h, k, seed):
     buf = np.zeros((rows, stride), np.uint8)
     buf[:h + 2 * MY, :w + 2 * MX] = np.pad(ref, ((MY, MY), (MX, MX)), mode="edge")
     srcs = [np.ascontiguousarray(np.roll(sc["src"], (3 * i, -5 * i), axis=(0, 1))) for i in range(k)]
+    if depth > 8:
+        # the same pictures with `depth` bits per sample: scaled up, the new low bits random (the margins stay replicas of the picture's edge)
+        rng = np.random.default_rng(seed)
+        sh = depth - 8
+        pic = (ref.astype(np.uint16) << sh) | rng.integers(0, 1 << sh, ref.shape, dtype=np.uint16)
+        buf = np.zeros((rows, stride), np.uint16)
+        buf[:h + 2 * MY, :w + 2 * MX] = np.pad(pic, ((MY, MY), (MX, MX)), mode="edge")
+        srcs = [np.ascontiguousarray((s.astype(np.uint16) << sh) | rng.integers(0, 1 << sh, s.shape, dtype=np.uint16)) for s in srcs]
     return buf, stride, rows, srcs
 
 
-def run_mode(hp, L, mode, w, h, k, S, reps, buf, stride, rows, srcs):
+def run_mode(hp, L, mode, w, h, k, S, reps, buf, stride, rows, srcs, depth=8):
     def stats():
         v = [C.c_uint64() for _ in range(4)]
         L.x265hip_sadsurf_stats(*[C.byref(x) for x in v])
         return [x.value for x in v]
     sps = []
     for s in srcs:
-        sp = L.x265hip_srcpic_create(8, w, h)
+        sp = L.x265hip_srcpic_create(depth, w, h)
         assert sp, L.x265hip_last_error()
         hp.check(L.x265hip_srcpic_upload(sp, s.ctypes.data, s.shape[1]))
         sps.append(sp)
     before = None
+    marks = []
     for rep in range(reps + 1):
+        marks.append(stats())
         if rep == 1:
-            before = stats()                      # the first repetition is the warm-up
-        rp = L.x265hip_refpic_create(8, w, h, stride, MX, MY, rows, buf.ctypes.data)
+            before = marks[-1]                    # the first repetition is the warm-up
+        rp = L.x265hip_refpic_create(depth, w, h, stride, MX, MY, rows, buf.ctypes.data)
         assert rp, L.x265hip_last_error()
         sss = []
         if mode == "frame":
@@ -91,6 +103,9 @@ def run_mode(hp, L, mode, w, h, k, S, reps, buf, stride, rows, srcs):
         L.x265hip_refpic_wait(rp)
         L.x265hip_refpic_destroy(rp)
     after = stats()
+    marks.append(after)
+    # the same per repetition (warm-up left out): the run-to-run spread of a launch
+    per_rep = [round((b[3] - a[3]) / max(b[2] - a[2], 1) / 1e3, 2) for a, b in zip(marks[1:-1], marks[2:])]
     for sp in sps:
         L.x265hip_srcpic_destroy(sp)
     rows_built = after[1] - before[1]
@@ -98,7 +113,7 @@ def run_mode(hp, L, mode, w, h, k, S, reps, buf, stride, rows, srcs):
     ns = after[3] - before[3]
     ctus = rows_built * ((w + 63) // 64)
     return {"mode": mode, "surfaces": k, "launches": launches, "ctus_per_launch": round(ctus / launches, 1), "us_per_launch": round(ns / launches / 1e3, 2),
-            "us_per_ctu_row": round(ns / rows_built / 1e3, 2), "ctus": ctus, "kernel_ns": ns}
+            "us_per_ctu_row": round(ns / rows_built / 1e3, 2), "ctus": ctus, "kernel_ns": ns, "us_per_launch_by_rep": per_rep}
 
 
 def main():
@@ -108,22 +123,25 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--range", type=int, default=32)
     ap.add_argument("--res", default="1920x1080")
+    ap.add_argument("--depth", type=int, default=8, choices=(8, 10, 12), help="bits per sample: 10 / 12 run sadsurf_ctu16_kernel (range <= 16) or sadsurf_ctu16_wide_kernel")
     a = ap.parse_args()
     import x265_amd.hipprim as hp
     L = hp.lib()
     hp.check(L.x265hip_init(0))
     w, h = map(int, a.res.split("x"))
-    buf, stride, rows, srcs = pictures(w, h, a.surfaces, 4321)
-    ub = unit_bytes(a.range)
+    buf, stride, rows, srcs = pictures(w, h, a.surfaces, 4321, a.depth)
+    ub = unit_bytes(a.range, a.depth)
     for mode in a.modes.split(","):
-        r = run_mode(hp, L, mode, w, h, a.surfaces, a.range, a.reps, buf, stride, rows, srcs)
+        r = run_mode(hp, L, mode, w, h, a.surfaces, a.range, a.reps, buf, stride, rows, srcs, a.depth)
+        r["depth"], r["range"] = a.depth, a.range
         secs = r["kernel_ns"] * 1e-9
         r["algorithmic_bytes_per_ctu"] = ub
         r["achieved_GBps"] = round(r["ctus"] * ub / secs / 1e9, 1)
         r["frac_of_hbm_peak"] = round(r["ctus"] * ub / secs / 1e9 / HBM_PEAK, 4)
         # 16 blocks x (2 S)^2 vectors x 256 absolute differences per CTU
         r["abs_diff_per_s_T"] = round(r["ctus"] * 16 * (2 * a.range) ** 2 * 256 / secs / 1e12, 2)
-        r["frac_of_valu_sad_ceiling"] = round(r["abs_diff_per_s_T"] / VALU_SAD_CEILING_T, 4)
+        if a.depth == 8:                      # (the ceiling is v_qsad_pk_u16_u8's; 16-bit pictures are measured with v_sad_u16)
+            r["frac_of_valu_sad_ceiling"] = round(r["abs_diff_per_s_T"] / VALU_SAD_CEILING_T, 4)
         print(json.dumps(r), flush=True)
 
 

@@ -17,7 +17,8 @@
 //   emit     the 16 x 16 window around each block's best vector is gathered out of the LDS surface (no second SAD pass) and written with the
 //            block's origin into the CTU row's chunk of the table buffer.
 // Values are pinned by tests/test_sadsurf.py (entries == sad<N, N> of the reference, pixel.cpp:40-55; origins == the same rule restated on the
-// CPU by the test tier).  16-bit pictures (Main10 / Main12 builds) have a kernel of their own below: v_sad_u16, u32 surfaces, range <= 16.
+// CPU by the test tier).  16-bit pictures (Main10 / Main12 builds) have a kernel of their own below: v_sad_u16, u32 surfaces — in LDS up to a range of 16, in
+// device memory above it.
 #include "common.h"
 #include "internal.h"
 #include "refpic.h"
@@ -540,16 +541,19 @@ __global__ __launch_bounds__(1024) void sadsurf_ctu_kernel(SurfArgs a)
 
 // ---- the same kernel for 16-bit pictures (Main10 / Main12 builds) --------------------------------------------------------------------------
 // v_qsad_pk_u16_u8 is a byte instruction; 16-bit samples are measured with v_sad_u16 (two absolute differences per lane and instruction), and a 16x16
-// SAD no longer fits 16 bits, so the surface holds u32 — 16 x (2 S)^2 x 4 bytes: S <= 16 keeps it in LDS (64 KB).  The reference window is staged twice,
+// SAD no longer fits 16 bits, so the surface holds u32 — 16 x (2 S)^2 x 4 bytes: S <= 16 keeps it in LDS (64 KB), see ss16_ctu for larger S.  The reference window is staged twice,
 // once as it is and once shifted by one sample, so that odd vectors read aligned dwords too.  A lane owns a 4 x 4 patch of vectors; the block's source
 // rows go through scalar registers eight at a time.  Decide and emit are the shared template.
-__global__ __launch_bounds__(1024) void sadsurf_ctu16_kernel(SurfArgs a)
+//
+// Ranges above 16 (S = 20 .. 32): 16 x (2 S)^2 x 4 bytes is up to 256 KB, more than a CU's LDS, so the surface of such a CTU lies in device memory — Wide: `surfaces`
+// is the workgroup's own region of a pooled buffer.  Stage and measure are the same code (the patch's sixteen results leave as four 16-byte global stores instead
+// of four LDS stores); decide and emit read the region through the same template (a workgroup lives on one CU: its stores are visible to its other waves behind the
+// barrier's workgroup-scope fence).  LDS then holds the source CTU and the two windows only: 76 KB at S = 32.  Measured: 3.4 x the S = 16 launch for 4 x the
+// vectors (profiles/r09_v1_sadsurf16_range.txt), which is why the surface is not cut into strips that fit LDS instead.
+template <bool Wide>
+__device__ __forceinline__ void ss16_ctu(const SurfArgs& a, unsigned char* smem, SsShared& sh, uint32_t* surfaces, int cx, int rowIn)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ SsShared sh;
-
-    int jn = 0, rowIn, cx;
-    surf_ctu(a.xcd, cx, rowIn);
+    int jn = 0;
     while (jn + 1 < a.nJobs && rowIn >= a.job[jn].rows) { rowIn -= a.job[jn].rows; jn++; }
     const SurfJob& jb = a.job[jn];
     const int S = jb.S, D = 2 * S;
@@ -557,7 +561,7 @@ __global__ __launch_bounds__(1024) void sadsurf_ctu16_kernel(SurfArgs a)
     uint32_t* sSrc = (uint32_t*)smem;                            // [64][32] dwords
     uint32_t* sRefA = sSrc + 64 * 32;                            // [64 + D][RWD]: dword k = samples (2k, 2k + 1) of the window row
     uint32_t* sRefB = sRefA + (64 + D) * RWD;                    // the same shifted by one sample: dword k = samples (2k + 1, 2k + 2)
-    uint32_t* sSurf = sRefB + (64 + D) * RWD;                    // [16][D][D]
+    uint32_t* sSurf = Wide ? surfaces : sRefB + (64 + D) * RWD;  // [16][D][D]
 
     const int cy = jb.row0 + rowIn;
     const int x0 = cx * 64, y0 = cy * 64;
@@ -667,6 +671,38 @@ __global__ __launch_bounds__(1024) void sadsurf_ctu16_kernel(SurfArgs a)
     __syncthreads();
 
     ss_decide_emit<uint32_t>(a, jb, sSurf, sh, S, x0, y0, cx, cy);
+}
+
+__global__ __launch_bounds__(1024) void sadsurf_ctu16_kernel(SurfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ SsShared sh;
+
+    int rowIn, cx;
+    surf_ctu(a.xcd, cx, rowIn);
+    ss16_ctu<false>(a, smem, sh, nullptr, cx, rowIn);
+}
+
+// The wide form's launch: a bounded 1-D grid (the pooled buffer holds one region of `regionElems` u32 per workgroup, so the grid is what the device can hold at
+// once, not the CTU count); workgroup g takes the CTUs g, g + grid, ... of the launch's `total` = cols x rows, in surf_ctu's XCD order restated for linear ids
+// (workgroup L of a round goes to XCD L % 8 when the grid is a multiple of 8; any grid gives a bijection).
+__global__ __launch_bounds__(1024) void sadsurf_ctu16_wide_kernel(SurfArgs a, uint32_t* surfaces, int64_t regionElems, int cols, int total)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ SsShared sh;
+
+    uint32_t* mine = surfaces + (int64_t)blockIdx.x * regionElems;
+    for (int L = blockIdx.x; L < total; L += gridDim.x)
+    {
+        int c = L;
+        if (a.xcd)
+        {
+            const int x = L & 7, i = L >> 3, per = total >> 3, rem = total & 7;
+            c = x * per + (x < rem ? x : rem) + i;
+        }
+        ss16_ctu<true>(a, smem, sh, mine, c % cols, c / cols);
+        __syncthreads();                                         // the next CTU's staging and measure overwrite what this one's emit reads
+    }
 }
 
 
@@ -988,6 +1024,49 @@ static size_t surf16_lds_bytes(int S)
     return (size_t)64 * 32 * 4 + (size_t)2 * (64 + D) * RWD * 4 + (size_t)16 * D * D * 4;
 }
 
+// the wide form (16-bit pictures, S > 16): the source CTU and the two windows; the surface is a region of a pooled device buffer
+static size_t surf16_wide_lds_bytes(int S)
+{
+    const int D = 2 * S, RWD = (64 + D) / 2 + 4;
+    return (size_t)64 * 32 * 4 + (size_t)2 * (64 + D) * RWD * 4;
+}
+static bool surf16_wide(int depth, int S) { return depth != 8 && S > 16; }
+
+// The wide form's surfaces: one buffer per launch in flight, `groups` regions of 16 x (2 maxS)^2 u32 (256 KB at S = 32).  A launch takes a buffer of its device
+// that no other launch holds — the workers of two places on one device, or a replica's stream next to its mirror's, may launch at the same time — and gives it
+// back once its stream is synchronised; buffers are kept for the next launch and only ever replaced by larger ones (device allocations cost milliseconds).
+struct WideBuf { int dev; size_t bytes; char* d; bool busy; };
+static std::vector<WideBuf> g_wide;                     // under g_poolLock
+static char* wide_take(int dev, size_t bytes)
+{
+    char* old = nullptr;
+    {
+        std::lock_guard<std::mutex> g(g_poolLock);
+        size_t small = g_wide.size();
+        for (size_t i = 0; i < g_wide.size(); i++)
+        {
+            WideBuf& b = g_wide[i];
+            if (b.busy || b.dev != dev) continue;
+            if (b.bytes >= bytes) { b.busy = true; return b.d; }
+            small = i;
+        }
+        if (small < g_wide.size()) { old = g_wide[small].d; g_wide[small] = g_wide.back(); g_wide.pop_back(); }
+    }
+    if (old) (void)device_free(old);                    // too small and idle: replaced (the caller has made `dev` current)
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    std::lock_guard<std::mutex> g(g_poolLock);
+    g_wide.push_back(WideBuf{ dev, bytes, d, true });
+    return d;
+}
+static void wide_return(char* d)
+{
+    if (!d) return;
+    std::lock_guard<std::mutex> g(g_poolLock);
+    for (WideBuf& b : g_wide)
+        if (b.d == d) b.busy = false;
+}
+
 static size_t surf_lds_bytes(int S)
 {
     const int D = 2 * S, RW = 64 + D + 8;
@@ -1084,6 +1163,7 @@ static void progress_multi(const std::vector<x265hip_refpic*>& rps)
     // same device, geometry and table layout next to each other (stable: the order of `rps` and of the surfaces inside a group is kept)
     auto same_group = [](const SurfItem& x, const SurfItem& y) {
         return x.dev == y.dev && x.ss->levels == y.ss->levels && x.rp->depth == y.rp->depth && x.rp->picW == y.rp->picW && x.rp->picH == y.rp->picH &&
+               surf16_wide(x.rp->depth, x.ss->S) == surf16_wide(y.rp->depth, y.ss->S) &&           // (a launch is of one kernel form)
                x.rp->marginX == y.rp->marginX && x.rp->marginY == y.rp->marginY && x.rp->bufRows == y.rp->bufRows && x.ss->lay.pitch == y.ss->lay.pitch; };
     {
         std::vector<SurfItem> sorted;
@@ -1207,7 +1287,8 @@ static void progress_multi(const std::vector<x265hip_refpic*>& rps)
             if (!(attrSet.load() >> dev & 1))
             {
                 if (hipFuncSetAttribute((const void*)sadsurf_ctu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf_lds_bytes(32)) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)sadsurf_ctu16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_lds_bytes(16)) != hipSuccess)
+                    hipFuncSetAttribute((const void*)sadsurf_ctu16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_lds_bytes(16)) != hipSuccess ||
+                    hipFuncSetAttribute((const void*)sadsurf_ctu16_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_wide_lds_bytes(32)) != hipSuccess)
                 {
                     set_error(X265HIP_EHIP, "sadsurf: cannot raise the dynamic LDS limit");
                     fail_refs(items, g0, g1);
@@ -1217,9 +1298,32 @@ static void progress_multi(const std::vector<x265hip_refpic*>& rps)
                 attrSet |= (uint64_t)1 << dev;
             }
             // the launch between two events of its own stream: the kernel's device time (x265hip_device_time, x265hip_sadsurf_stats)
+            // the wide form: as many workgroups as the device holds at once (one per free CU: 16 waves of 128 registers), each with a region of the pooled buffer;
+            // X265HIP_SADSURF_WIDE_GROUPS bounds the grid further (read per launch: the tests walk several CTUs per workgroup on small pictures with it)
+            const bool wide = surf16_wide(rp0->depth, maxS);
+            char* wideBuf = nullptr;
+            int wideGroups = 0;
+            const int64_t regionElems = (int64_t)16 * (2 * maxS) * (2 * maxS);
+            if (wide)
+            {
+                const int total = lay.ctuCols * rows, cap = getenv("X265HIP_SADSURF_WIDE_GROUPS") ? atoi(getenv("X265HIP_SADSURF_WIDE_GROUPS")) : 0;
+                wideGroups = free_compute_units(dev);
+                if (cap > 0 && cap < wideGroups) wideGroups = cap;
+                if (total < wideGroups) wideGroups = total;
+                if (!(wideBuf = wide_take(dev, (size_t)wideGroups * regionElems * 4)))
+                {
+                    set_error(X265HIP_ENOMEM, "sadsurf: %zu bytes for the surfaces of a launch at range %d", (size_t)wideGroups * regionElems * 4, maxS);
+                    fail_refs(items, g0, g1);
+                    (void)hipSetDevice(rp0->device);
+                    return;
+                }
+            }
             DevSpan span(X265HIP_CLK_SADSURF, st);
             if (rp0->depth == 8)
                 hipLaunchKernelGGL(sadsurf_ctu_kernel, dim3(lay.ctuCols, rows), dim3(1024), surf_lds_bytes(maxS), st, a);
+            else if (wide)
+                hipLaunchKernelGGL(sadsurf_ctu16_wide_kernel, dim3(wideGroups), dim3(1024), surf16_wide_lds_bytes(maxS), st, a, (uint32_t*)wideBuf, regionElems, lay.ctuCols,
+                                   lay.ctuCols * rows);
             else
                 hipLaunchKernelGGL(sadsurf_ctu16_kernel, dim3(lay.ctuCols, rows), dim3(1024), surf16_lds_bytes(maxS), st, a);
             bool bad = hipGetLastError() != hipSuccess;
@@ -1277,7 +1381,7 @@ static void progress_multi(const std::vector<x265hip_refpic*>& rps)
                 // SURVEY.md §8d, "batched exhaustive search of one block over an R x R window counts the unique footprint", applied to what a workgroup
                 // stages: ONE 64x64 source block and ONE (64 + R - 1)^2 window per CTU (R = 2 S; the 16x16 / 32x32 / 64x64 searches of the CTU all read
                 // that one staging, the 32 / 64 SADs are sums of the 16x16 ones), plus the bytes the CTU really emits: a 16 x 16 window of entries and an
-                // origin per block of the levels built (the surfaces themselves never leave LDS)
+                // origin per block of the levels built (the surfaces themselves never leave LDS; the wide form's region of device memory is working storage, not counted)
                 const int64_t R = 2 * a.job[k].S;
                 span.bytes += (uint64_t)a.job[k].rows * lay.ctuCols * (64 * 64 + (64 + R - 1) * (64 + R - 1)) * rp0->B;
                 for (int l = a.job[k].level0 ? 0 : 1; l < 4; l++)
@@ -1295,7 +1399,9 @@ static void progress_multi(const std::vector<x265hip_refpic*>& rps)
                 const size_t off = (size_t)a.job[k].row0 * lay.pitch, bytes = (size_t)a.job[k].rows * lay.pitch;
                 bad = hipMemcpyAsync(ss->hBuf + off, ss->dBuf + off, bytes, hipMemcpyDeviceToHost, st) != hipSuccess;
             }
-            if (bad || hipStreamSynchronize(st) != hipSuccess)
+            const bool synced = hipStreamSynchronize(st) == hipSuccess && !bad;   // (waited for either way: the pooled buffer goes back only when nothing writes it)
+            wide_return(wideBuf);                             // (after a failed synchronisation the reference pictures are failed and nothing launches on them again)
+            if (!synced)
             {
                 set_error(X265HIP_EHIP, "sadsurf: launch, copy or synchronisation failed");
                 fail_refs(items, g0, g1);
@@ -1527,10 +1633,10 @@ x265hip_sadsurf* x265hip_sadsurf_attach(x265hip_srcpic* src, x265hip_refpic* ref
 x265hip_sadsurf* x265hip_sadsurf_attach_levels(x265hip_srcpic* src, x265hip_refpic* ref, int searchRange, int lambda20, int levels)
 {
     if (ensure_device()) return nullptr;
-    if (!src || !ref || src->depth != ref->depth || src->w != ref->picW || src->h != ref->picH || searchRange < 8 || searchRange > (src->depth == 8 ? 32 : 16) || (searchRange & 3) ||
+    if (!src || !ref || src->depth != ref->depth || src->w != ref->picW || src->h != ref->picH || searchRange < 8 || searchRange > 32 || (searchRange & 3) ||
         lambda20 < 0 || lambda20 > (1 << 20) || ref->marginX < searchRange + 8 || ref->marginY < searchRange || (levels & ~31) || (levels & 14) != 14 || ((levels & 1) && src->depth != 8))
     {
-        set_error(X265HIP_EINVAL, "x265hip_sadsurf_attach: pictures do not match, or range %d (8..32 for 8-bit pictures, 8..16 for 16-bit ones) / lambda %d / margins out of bounds", searchRange, lambda20);
+        set_error(X265HIP_EINVAL, "x265hip_sadsurf_attach: pictures do not match, or range %d (8..32, a multiple of 4) / lambda %d / margins out of bounds", searchRange, lambda20);
         return nullptr;
     }
     x265hip_sadsurf* ss = new x265hip_sadsurf;

@@ -83,7 +83,7 @@ bool g_subpelHit = false;        // X265HIP_DEBUG_SUBPELHIT=1: how many served s
 std::atomic<uint64_t> g_spHit[4], g_spAll[4];
 std::atomic<uint64_t> g_spDist[4][5];
 bool g_verify = false;           // X265HIP_VERIFY=1: every looked-up SAD is recomputed with the C function and compared (debugging self-check)
-int g_range = 32;                // X265HIP_SADPLANES_RANGE: the exhaustive search that places the windows covers [-range, range)^2
+int g_range = X265_DEPTH == 8 ? 32 : 16;   // X265HIP_SADPLANES_RANGE (8..32 in every build): the exhaustive search that places the windows covers [-range, range)^2
 EncoderPrimitives g_c;
 std::mutex g_lock;
 
@@ -183,6 +183,7 @@ void report()
             (unsigned long long)attached, (unsigned long long)rows, (unsigned long long)launches, kernelNs * 1e-6, (unsigned long long)m, (unsigned long long)un);
     fprintf(stderr, "x265hip: sadplanes: %llu sub-pel SATDs of the motion search (filter + satd) served from GPU-built tables around the windows' centres, %llu of the same "
                     "searches elsewhere computed on the host\n", (unsigned long long)g_subHit.load(), (unsigned long long)g_subMiss.load());
+    fprintf(stderr, "x265hip: sadplanes: search range +-%d (levels %d)\n", g_range, g_levels);
     if (g_rectSearches.load())
         fprintf(stderr, "x265hip: sadplanes: rectangular / asymmetric PUs: %llu searches, %llu integer-pel SADs served as sums of their squares' entries, %llu with a square's "
                         "window elsewhere computed on the host\n", (unsigned long long)g_rectSearches.load(), (unsigned long long)g_rectHit.load(), (unsigned long long)g_rectMiss.load());
@@ -230,12 +231,9 @@ bool decide()
         if (g_range < 8) g_range = 8;
         if (g_range > 32) g_range = 32;
         g_range &= ~3;
-        // 16-bit builds (Main10 / Main12): the device keeps a CTU's u32 surface in LDS up to a range of 16, and has no 8x8 level
+        // 16-bit builds (Main10 / Main12): the device has no 8x8 level (and keeps a CTU's u32 surface in LDS up to a range of 16, in device memory above: the default)
         if (X265_DEPTH != 8)
-        {
-            if (g_range > 16) g_range = 16;
             g_levels &= 14;
-        }
         if ((env && !strcmp(env, "0")) || (all && !strcmp(all, "0")) || (table && !strcmp(table, "percall")) || !g_levels ||
             x265hip_device_count() < 1)
             g_state = -1;
