@@ -966,7 +966,7 @@ X265HIP_HD static inline int x265hipi_cujob_denoise_offset(const x265hip_cujob* 
 /* the chroma formats this library's CU jobs accept: bit f set for x265hip_cujob::chroma == f (0xF here).  Needs no device. */
 uint32_t x265hip_cujob_formats(void);
 /* what else this library's CU jobs can do: bit 0 = table sets of scaling lists (x265hip_cujob::scaling), bit 1 = noise reduction (X265HIP_CUJOB_DENOISE,
- * x265hip_cujob_denoise).  Needs no device. */
+ * x265hip_cujob_denoise), bit 2 = intra scans split over the slot's two workgroups (X265HIP_INTRAJOB_SPLIT).  Needs no device. */
 uint32_t x265hip_cujob_features(void);
 /* A table set = the quantiser and dequantiser matrices of the inter lists a job uses, packed [size 8, 16, 32][plane Y, Cb, Cr][rem 0..5][n * n] (rows
  * contiguous: ScalingList::m_quantCoef / m_dequantCoef [1..3][3..5][0..5] as the encoder holds them, scalinglist.cpp:342-415).  quant_c multiplies in int:
@@ -1059,14 +1059,18 @@ int x265hip_cuserve_submit_sao(x265hip_cuserve* cs, int slot, const x265hip_saoj
  * Pixel block (samples: bytes at 8 bit, uint16_t above): the unfiltered neighbour line in the reference's array layout (Predict::initAdiPattern:
  * [0] corner, [1..2N] top + top-right, [2N+1..4N] left + bottom-left) at sample 0, the [1 2 1] filtered line at sample 4N + 16, the N x N source
  * block (stride N) at sample 2 * (4N + 16).  Results: units[0].ready = units[0].readyInv = the ticket; the 35 costs as int32 at the start of
- * the slot's `levels` block (cost of mode m at index m). */
+ * the slot's `levels` block (cost of mode m at index m).
+ * X265HIP_INTRAJOB_SPLIT in `flags` (x265hip_cujob_features() bit 2; log2Size 4 and 5 — with log2Size 3: X265HIP_EINVAL): the scan is shared by the two
+ * workgroups that serve the slot.  Planar, DC and modes 2-17 are in place when units[0].ready == the ticket, modes 18-34 when units[1].ready == the ticket
+ * (same indices of `levels`); the two words arrive in either order and the caller waits for both. */
 #define X265HIP_INTRAJOB_MARK 0x100u
+#define X265HIP_INTRAJOB_SPLIT 1u
 typedef struct x265hip_intrajob
 {
     uint32_t bitDepth;      /* 8, 10 or 12 */
     uint32_t mark;          /* X265HIP_INTRAJOB_MARK: where an SAO statistics job holds its plane count (both kinds travel under the same ticket class) */
     uint32_t log2Size;      /* 3, 4 or 5 */
-    uint32_t reserved;
+    uint32_t flags;         /* 0 or X265HIP_INTRAJOB_SPLIT (the word was `reserved`, always 0, before split scans) */
 } x265hip_intrajob;
 X265HIP_HD static inline int x265hipi_intrajob_line_samples(int log2Size) { return (4 << log2Size) + 16; }
 X265HIP_HD static inline int x265hipi_intrajob_pixel_bytes(const x265hip_intrajob* j)

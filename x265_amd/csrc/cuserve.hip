@@ -139,11 +139,15 @@ static_assert(sizeof(x265hip_cujob) <= 128, "job header");
 // needs to know before it has read anything: log2CUSize - 4 (bits 1..0), chroma (bit 2), 16-bit samples (bit 3), an inverse job's levels block (bit 4),
 // the chroma format beyond 4:2:0 (bits 6..5: x265hip_cujob::chroma - 1 of a job with chroma, so 4:2:0 and 4:0:0 tickets are what they always were), a table
 // set to quantise with (bit 7: flat jobs' tickets are what they always were)
-// bits 1..0 == 3: an SAO statistics job (x265hip_saojob): bits 7..2 = the job's size, header included, in 512-byte steps
+// bits 1..0 == 3: an SAO statistics job (x265hip_saojob) or an intra scan job: bits 7..2 = the job's size, header included, in 512-byte steps (an SAO job
+// has up to 49 of them, an intra scan up to 6)
+// bits 7..5 all set (a size no SAO job has): an intra scan split over the slot's pair (X265HIP_INTRAJOB_SPLIT), its size in bits 4..2 — role 1 learns from the
+// ticket alone that it has a share
+__host__ __device__ inline bool ticket_split_intra(uint32_t t) { return (t & 0xe3u) == 0xe3u; }
 __host__ __device__ inline uint32_t ticket_format(uint32_t t) { return (t & 4) ? 1 + ((t >> 5) & 3) : 0; }      // x265hip_cujob::chroma of a CU job's ticket
 __host__ __device__ inline uint32_t ticket_bytes(uint32_t t)
 {
-    if ((t & 3) == 3) return ((t >> 2) & 63u) * 512u - 128u;
+    if ((t & 3) == 3) return ((t >> 2) & (ticket_split_intra(t) ? 7u : 63u)) * 512u - 128u;
     const uint32_t n2 = 1u << (2 * ((t & 3) + 4)), elems = n2 + 2 * (uint32_t)x265hipi_cujob_chroma_elems(ticket_format(t), (int)n2);
     return 2 * elems * ((t & 8) ? 2 : 1);
 }
@@ -151,6 +155,8 @@ __host__ __device__ inline uint32_t ticket_bytes(uint32_t t)
 // steps of 512 bytes (a 64th would spill into the running number), so the CU jobs' larger blocks change nothing for these jobs
 constexpr int kSaoPixelBytes = 2 * 6144 * 2;
 static_assert(kSaoPixelBytes <= X265HIP_CUJOB_PIXEL_BYTES && (128 + kSaoPixelBytes) / 512 <= 63, "SAO statistics job: pixel block, ticket size field");
+// ... and its largest size field stays below 56 (bits 7..5 all set), the mark of a split intra scan: an SAO ticket is never taken for one
+static_assert((128 + kSaoPixelBytes + 511) / 512 < 56, "SAO statistics job: the size field must stay clear of ticket_split_intra's mark");
 
 // qTab / dqTab: the unit's (size, plane, rem) matrices of the job's table set (x265hip_cujob::scaling), n * n int32 each, rows contiguous; null: the flat quantiser.
 // per: the plane's qpParam.per, which dequant_scaling takes apart from the matrix
@@ -1682,8 +1688,11 @@ __device__ __forceinline__ void run_sao(SlotOut* s, JobLds& L, uint32_t seq, uin
 // ---- intra mode scan jobs (x265hip_intrajob): sa8d of all 35 predictions of one block, intra.hip's intra_scan_kernel with the lines and the source block
 // in the job's LDS copy.  A lane = one 4x4 tile whose 16 predicted samples are made in registers; a 32x32 block is one mode per wave and pass (9 passes of
 // the workgroup), a 16x16 block four modes per wave (3 passes), an 8x8 block sixteen (1 pass).
+// share 0: all 35 modes, answered through units[0].  A split scan (ticket_split_intra) is measured by both workgroups of the slot, each from its own LDS copy of
+// the job: share 1 (role 0) = planar, DC and modes 2-17, units[0]; share 2 (role 1) = modes 18-34, units[1] — 5 passes instead of 9 for 32x32, 2 instead of 3
+// for 16x16.  The shares' cost indices are disjoint, neither workgroup waits for the other, the host waits for both ready words.
 template <typename P>
-__device__ __forceinline__ void run_intra(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0)
+__device__ __forceinline__ void run_intra(SlotOut* s, JobLds& L, uint32_t seq, uint64_t t0, int share)
 {
     const x265hip_intrajob& j = *reinterpret_cast<const x265hip_intrajob*>(&L.job);
     const int log2n = (int)j.log2Size, n = 1 << log2n, n2 = 2 * n, depth = (int)j.bitDepth, maxv = (1 << depth) - 1;
@@ -1721,10 +1730,11 @@ __device__ __forceinline__ void run_intra(SlotOut* s, JobLds& L, uint32_t seq, u
     for (int i = 1; i <= n; i++)
         dcv += (int)cr[i] + (int)cr[-i];
     dcv >>= log2n + 1;
-    for (int base = 0; base < 35; base += 4 * jpw)
+    const int first = share == 2 ? 18 : 0, end = share == 1 ? 18 : 35, unit = share == 2 ? 1 : 0;
+    for (int base = first; base < end; base += 4 * jpw)
     {
         const int want = base + wave * jpw + lane / T;
-        const bool ok = want < 35;
+        const bool ok = want < end;
         const int mode = ok ? want : 34;
         int m[16];
         // ---- the angular prediction of every lane's mode, branch-free (modes 0 and 1 run it as mode 2 and are overwritten below).  intra_dev.h's
@@ -1798,22 +1808,24 @@ __device__ __forceinline__ void run_intra(SlotOut* s, JobLds& L, uint32_t seq, u
     if (tid < 64)
     {
         int32_t* out = reinterpret_cast<int32_t*>(s->levels);
-        if (tid < 35)
+        if (tid >= first && tid < end)
             out[tid] = costs[tid];
+        // one wave carries the share out: its own stores are waited for (s_waitcnt vmcnt(0) is per wave), then lane 0 publishes
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         if (tid == 0)
         {
-            s->units[0].fwdTicks = (uint32_t)(wall_clock64() - t0);
-            __hip_atomic_store(&s->units[0].readyInv, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&s->units[0].ready, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            s->units[unit].fwdTicks = (uint32_t)(wall_clock64() - t0);
+            __hip_atomic_store(&s->units[unit].readyInv, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&s->units[unit].ready, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
     __syncthreads();
 }
 
 // one job: `ticket` says how many bytes the job holds, so header and pixels arrive in one round trip.  role 0 / 1: this workgroup's half of a CU job (luma /
-// chroma: each fetches the header and its own planes only); SAO statistics and intra scans are role 0's alone
+// chroma: each fetches the header and its own planes only); SAO statistics and unsplit intra scans are role 0's alone, a split intra scan (ticket_split_intra) is
+// copied whole by both roles, which measure half of the modes each
 // SETS: the kernel was started for a service with table sets or denoise jobs (cu_server_kernel_sets / cu_job_kernel_sets) and holds the SC and DN instantiations
 // beside the flat ones
 template <bool SETS>
@@ -1821,7 +1833,8 @@ __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L
 {
     const int tid = threadIdx.x;
     const bool cuJob = (ticket & 3) != 3;
-    if (role && (!cuJob || !(ticket & 4)))
+    const bool splitIntra = !cuJob && ticket_split_intra(ticket);
+    if (role && (cuJob ? !(ticket & 4) : !splitIntra))
         return;                                                              // nothing of this job is role 1's (uniform over the workgroup)
     const uint64_t t0 = wall_clock64();
     const uint4* in = reinterpret_cast<const uint4*>(&sin->job);
@@ -1853,8 +1866,8 @@ __device__ __forceinline__ void run_job(const SlotIn* sin, SlotOut* s, JobLds& L
     {
         const x265hip_intrajob& ij = *reinterpret_cast<const x265hip_intrajob*>(&L.job);
         if (!(ij.mark & X265HIP_INTRAJOB_MARK)) { if (ij.bitDepth > 8) run_sao<uint16_t>(s, L, ticket, t0); else run_sao<uint8_t>(s, L, ticket, t0); }
-        else if (ij.bitDepth > 8) run_intra<uint16_t>(s, L, ticket, t0);
-        else run_intra<uint8_t>(s, L, ticket, t0);
+        else if (ij.bitDepth > 8) run_intra<uint16_t>(s, L, ticket, t0, splitIntra ? 1 + role : 0);
+        else run_intra<uint8_t>(s, L, ticket, t0, splitIntra ? 1 + role : 0);
     }
     // bit 7 of the ticket: a job with a table set whose units the DEVICE quantises or dequantises (in coefficient mode the host does both: the id is carried and
     // unused).  Flat jobs run the instantiation they always ran
@@ -1923,6 +1936,8 @@ __device__ __forceinline__ void serve(JobLds& L, const SlotIn* ins, SlotOut* out
             const uint32_t sHi = trMax < 5 ? (trMax < log2cu ? trMax : log2cu) : (log2cu < 5 ? log2cu : 5);
             firstUnit = 1 << (2 * (log2cu - sHi));
         }
+        else if (role && last && last != 0xffffffffu && ticket_split_intra(last))
+            firstUnit = 1;                                                   // (a split intra scan: role 1's share is answered through units[1])
         else if (role)
             firstUnit = -1;                                                  // (not a job role 1 has a share in: nothing to look at)
         if (firstUnit >= 0 && last && last != 0xffffffffu && __hip_atomic_load(&s->units[firstUnit].ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) != last)
@@ -2376,7 +2391,7 @@ uint32_t x265hip_cujob_formats(void)
 
 uint32_t x265hip_cujob_features(void)
 {
-    return 1u | 2u;                                                                          // bit 0: table sets of scaling lists (x265hip_cujob::scaling); bit 1: X265HIP_CUJOB_DENOISE
+    return 1u | 2u | 4u;                                      // bit 0: table sets of scaling lists (x265hip_cujob::scaling); bit 1: X265HIP_CUJOB_DENOISE; bit 2: X265HIP_INTRAJOB_SPLIT
 }
 
 int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef)
@@ -2509,13 +2524,17 @@ int x265hip_cuserve_submit_intra(x265hip_cuserve* cs, int slot, const x265hip_in
     if (!cs || slot < 0 || slot >= cs->slots || !job || !seqOut) return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit_intra: slot %d", slot);
     if ((job->bitDepth != 8 && job->bitDepth != 10 && job->bitDepth != 12) || job->mark != X265HIP_INTRAJOB_MARK || job->log2Size < 3 || job->log2Size > 5)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit_intra: depth %u, mark %#x, log2 size %u", job->bitDepth, job->mark, job->log2Size);
+    // (an 8x8 scan is one pass of one workgroup already: nothing to split)
+    if ((job->flags & X265HIP_INTRAJOB_SPLIT) && job->log2Size < 4)
+        return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit_intra: flags %#x, log2 size %u", job->flags, job->log2Size);
+    const bool split = (job->flags & X265HIP_INTRAJOB_SPLIT) != 0;
     const int bytes = x265hipi_intrajob_pixel_bytes(job);
     SlotIn* s = cs->in + slot;
     uint32_t run = cs->seq[slot].load(std::memory_order_relaxed) + 1;
     if (run >= 0xfffff0u) run = 1;
     cs->seq[slot].store(run, std::memory_order_relaxed);
     const uint32_t steps = (uint32_t)(128 + bytes + 511) / 512;
-    const uint32_t seq = (run << 8) | 3u | (steps << 2);
+    const uint32_t seq = (run << 8) | 3u | (steps << 2) | (split ? 0xe0u : 0u);                 // (steps <= 6: bits 7..5 are the split mark's, ticket_split_intra)
     *seqOut = seq;
     cs->jobs.fetch_add(1, std::memory_order_relaxed);
     cs->intraJobs.fetch_add(1, std::memory_order_relaxed);

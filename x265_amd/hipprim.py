@@ -285,10 +285,11 @@ SAOJOB_STATS_ENTRIES = 3 * 5 * 32
 
 class IntraScanJob(C.Structure):
     """x265hip_intrajob (include/x265hip.h): the 35-mode sa8d scan of one block as a job of the CU-job service"""
-    _fields_ = [("bitDepth", u32), ("mark", u32), ("log2Size", u32), ("reserved", u32)]
+    _fields_ = [("bitDepth", u32), ("mark", u32), ("log2Size", u32), ("flags", u32)]
 
 
 INTRAJOB_MARK = 0x100
+INTRAJOB_SPLIT = 1                # IntraScanJob.flags: the scan is shared by the slot's two workgroups (x265hip_cujob_features() bit 2)
 
 
 class CuJobUnit(C.Structure):

@@ -1,7 +1,7 @@
 // x265_hip_cuserve.h — what the three translation units of the job-service seams share (not an installed header: internal to x265_amd/host):
 //   x265_hip_cuserve.cpp    the services and their slots, CU residual quad-tree jobs (Search::estimateResidualQT / encodeResAndCalcRd*CU / predInterSearch, Quant::*)
 //   x265_hip_saostats.cpp   SAO statistics jobs (SAO::calcSaoStatsCTU)
-//   x265_hip_intrascan.cpp  intra mode scan jobs (Search::checkIntraInInter and the table slots it answers through)
+//   x265_hip_intrascan.cpp  intra mode scan jobs (Search::checkIntraInInter, Search::checkIntra and the table slots they answer through)
 #pragma once
 #include <atomic>
 #include <ctime>
@@ -51,6 +51,7 @@ extern void refEstimateResidualQT(Search* self, Mode& mode, const CUGeom& cuGeom
                                   const uint32_t depthRange[2], int32_t splitMore)
     asm("_ZN4x2659SearchRef18estimateResidualQTERNS_4ModeERKNS_6CUGeomEjjRNS_8ShortYuvERNS0_4CostEPKji");
 extern void refCheckIntraInInter(Search* self, Mode& intraMode, const CUGeom& cuGeom) asm("_ZN4x2659SearchRef17checkIntraInInterERNS_4ModeERKNS_6CUGeomE");
+extern void refCheckIntra(Search* self, Mode& intraMode, const CUGeom& cuGeom, PartSize partSize) asm("_ZN4x2656Search14checkIntraBodyERNS_4ModeERKNS_6CUGeomENS_8PartSizeE");
 extern void refEncodeResAndCalcRdInterCU(Search* self, Mode& interMode, const CUGeom& cuGeom) asm("_ZN4x2656Search29encodeResAndCalcRdInterCUBodyERNS_4ModeERKNS_6CUGeomE");
 extern void refEncodeResAndCalcRdSkipCU(Search* self, Mode& interMode) asm("_ZN4x2656Search28encodeResAndCalcRdSkipCUBodyERNS_4ModeE");
 extern void refPredInterSearch(Search* self, Mode& interMode, const CUGeom& cuGeom, bool bChromaMC, uint32_t refMasks[2])

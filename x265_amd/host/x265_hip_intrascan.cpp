@@ -1,5 +1,5 @@
-// x265_hip_intrascan.cpp — the intra mode scan of Search::checkIntraInInter as jobs of the CU-job service (split from x265_hip_cuserve.cpp in round 6;
-// INTEGRATION.md §6l).
+// x265_hip_intrascan.cpp — the intra mode scan of Search::checkIntraInInter and of Search::checkIntra (estIntraPredQT) as jobs of the CU-job service (split
+// from x265_hip_cuserve.cpp in round 6).
 #include "x265_hip_cuserve.h"
 
 namespace X265_NS {
@@ -24,37 +24,61 @@ bool g_intraAhead = true;            // X265HIP_INTRASCAN_AHEAD=0: the job leave
 int g_intraMinLog2 = 4;              // X265HIP_INTRASCAN_MIN=<log2>: smallest block handed over (an 8x8 scan is ~8 us of host code: less than a round trip)
 bool g_intraAheadPredict = true;     // X265HIP_INTRASCAN_AHEAD=2: no prediction of whether the intra try will come, every candidate CU's job leaves
 int g_intraSyncMinLog2 = 5;          // ... and the smallest one handed over when no job is ahead (the thread waits a whole round trip)
-struct alignas(64) IntraCounters { std::atomic<uint64_t> jobs, served, ahead, aheadHit, dropped, waits, waitCycles, host, aheadBy[2]; };
-IntraCounters g_intraCount[16];
+bool g_intraCheckIntra = false;      // X265HIP_INTRASCAN_CHECKINTRA=1: Search::checkIntra's scans (I slices, the intra try of RD 5-6) are served too
+bool g_intraSplit = false;           // X265HIP_INTRASCAN_SPLIT=1 and the library has them (x265hip_cujob_features bit 2): scans >= 16x16 leave as X265HIP_INTRAJOB_SPLIT jobs.
+                                     // Off by default: 10.8 -> 8.3 us and 27.0 -> 16.5 us on the device, but the bench encode was not ahead with them
+// two families of counters: [0] the scans of checkIntraInInter (the `intrascan:` line), [1] those of checkIntra (a line of their own)
+struct alignas(64) IntraCounters { std::atomic<uint64_t> jobs, served, ahead, aheadHit, dropped, waits, waitCycles, host, aheadBy[2], split, servedI; };
+IntraCounters g_intraCount[2][16];
 constexpr int kIntraMaxSamples = 2 * (4 * 32 + 16) + 32 * 32;
 struct IntraJob
 {
     bool active;
+    bool split;                       // an X265HIP_INTRAJOB_SPLIT job: done when units[0] AND units[1] carry the ticket
+    int family;                       // whose counters it is counted in
     Service* svc; int slot; uint32_t seq;
     int log2n;
     pixel sent[kIntraMaxSamples];     // what the device was given: raw line, filtered line, source block
 };
-// inside refCheckIntraInInter of a served block: what the table slots answer from
-struct IntraCtx { bool active, allangs, verify; const pixel* predBuf; const pixel* fencT; int n, lastMode; const int32_t* costs; };
+// inside refCheckIntraInInter / refCheckIntra of a served block: what the table slots answer from.  predOne: where DC, planar and a table without
+// intra_pred_allangs put ONE prediction (checkIntraInInter: m_intraPredAngs, estIntraPredQT: m_intraPred); predBuf: the all-angles buffer (m_intraPredAngs);
+// left: cost answers until the scan is over (estIntraPredQT goes on with RD tries under the same context: 35, then the slots pass everything through)
+struct IntraCtx { bool active, allangs, verify; const pixel* predOne; const pixel* predBuf; const pixel* fencT; int n, lastMode, left; const int32_t* costs; };
 __attribute__((tls_model("initial-exec"))) thread_local IntraJob t_intra;
+// Search::checkIntra's jobs, one per block size (8, 16, 32): at RD 5-6 a CU's job leaves BEFORE its sub-CUs are analysed (intra_ahead), so a 32x32 CU's job is
+// out while its 16x16 sub-CUs send, adopt and hand back theirs
+__attribute__((tls_model("initial-exec"))) thread_local IntraJob t_intraCI[3];
 __attribute__((tls_model("initial-exec"))) thread_local IntraCtx t_ictx;
 
-inline IntraCounters& intra_counters() { touch_shard(); return g_intraCount[t_shard & 15]; }
+inline IntraCounters& intra_counters(int family = 0) { touch_shard(); return g_intraCount[family][t_shard & 15]; }
 
 void intra_report()
 {
     uint64_t jobs = 0, served = 0, ah = 0, hit = 0, dr = 0, w = 0, wc = 0, host = 0, ab[2] = { 0, 0 };
     for (int i = 0; i < 16; i++)
     {
-        for (int k = 0; k < 2; k++) ab[k] += g_intraCount[i].aheadBy[k];
-        jobs += g_intraCount[i].jobs; served += g_intraCount[i].served; ah += g_intraCount[i].ahead; hit += g_intraCount[i].aheadHit; dr += g_intraCount[i].dropped;
-        w += g_intraCount[i].waits; wc += g_intraCount[i].waitCycles; host += g_intraCount[i].host;
+        const IntraCounters& c = g_intraCount[0][i];
+        for (int k = 0; k < 2; k++) ab[k] += c.aheadBy[k];
+        jobs += c.jobs; served += c.served; ah += c.ahead; hit += c.aheadHit; dr += c.dropped;
+        w += c.waits; wc += c.waitCycles; host += c.host;
     }
     fprintf(stderr, "x265hip: intrascan: the 35-mode sa8d scans of %llu blocks >= %dx%d (Search::checkIntraInInter) measured by the GPU in %llu jobs, %llu scans on the host; %llu jobs "
                     "left ahead when predInterSearch was entered, %llu of them adopted, %llu never asked for; %llu waits of %.0f cycles on average\n",
             (unsigned long long)served, 1 << g_intraMinLog2, 1 << g_intraMinLog2, (unsigned long long)jobs, (unsigned long long)host, (unsigned long long)ah, (unsigned long long)hit,
             (unsigned long long)dr, (unsigned long long)w, w ? (double)wc / w : 0.0);
     fprintf(stderr, "x265hip: intrascan: %llu candidate CUs sent no job ahead because no sub-CU of theirs had chosen intra (analysis.cpp:1633: --limit-refs)\n", (unsigned long long)ab[0]);
+    // the scans of Search::checkIntra (every CU of an I slice, the intra try of RD levels 5-6), X265HIP_INTRASCAN_CHECKINTRA
+    uint64_t t[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, splitAll = 0;
+    for (int i = 0; i < 16; i++)
+    {
+        const IntraCounters& c = g_intraCount[1][i];
+        t[0] += c.served; t[1] += c.jobs; t[2] += c.host; t[3] += c.ahead; t[4] += c.aheadHit; t[5] += c.dropped; t[6] += c.waits; t[7] += c.waitCycles; t[8] += c.split; t[9] += c.servedI;
+        splitAll += c.split + g_intraCount[0][i].split;
+    }
+    fprintf(stderr, "x265hip: intrascan: Search::checkIntra (%s): %llu scans served by the GPU in %llu jobs (%llu of the scans in I slices, where nothing can leave ahead), %llu scans on the host; %llu jobs left ahead when predInterSearch was "
+                    "entered, %llu of them adopted, %llu never asked for; %llu waits of %.0f cycles on average; %llu split jobs (%llu with checkIntraInInter's)\n",
+            g_intraCheckIntra ? "on" : "off", (unsigned long long)t[0], (unsigned long long)t[1], (unsigned long long)t[9], (unsigned long long)t[2], (unsigned long long)t[3], (unsigned long long)t[4],
+            (unsigned long long)t[5], (unsigned long long)t[6], t[6] ? (double)t[7] / t[6] : 0.0, (unsigned long long)t[8], (unsigned long long)splitAll);
 }
 
 bool intra_enabled()
@@ -70,6 +94,9 @@ bool intra_enabled()
             if (getenv("X265HIP_INTRASCAN_AHEAD")) { g_intraAhead = atoi(getenv("X265HIP_INTRASCAN_AHEAD")) != 0; g_intraAheadPredict = atoi(getenv("X265HIP_INTRASCAN_AHEAD")) != 2; }
             if (getenv("X265HIP_INTRASCAN_MIN")) g_intraMinLog2 = x265_clip3(3, 5, atoi(getenv("X265HIP_INTRASCAN_MIN")));
             if (getenv("X265HIP_INTRASCAN_SYNC_MIN")) g_intraSyncMinLog2 = x265_clip3(3, 6, atoi(getenv("X265HIP_INTRASCAN_SYNC_MIN")));
+            if (getenv("X265HIP_INTRASCAN_CHECKINTRA")) g_intraCheckIntra = atoi(getenv("X265HIP_INTRASCAN_CHECKINTRA")) != 0;
+            const char* sp = getenv("X265HIP_INTRASCAN_SPLIT");
+            g_intraSplit = x265hip_cujob_features && (x265hip_cujob_features() & 4) && sp && atoi(sp) != 0;
             if ((env && !strcmp(env, "0")) || (all && !strcmp(all, "0")) || (table && !strcmp(table, "percall")))
                 g_intraState = -1;
             else
@@ -93,14 +120,19 @@ bool intra_enabled()
 }
 
 // waits for this thread's intra job; false: the device did not deliver (the slot is kept: the device may still write into it)
+// (a split job's two shares arrive in either order: both ready words)
+inline bool intra_ready(Service* svc, int slot, uint32_t seq, bool split)
+{
+    const x265hip_cujob_unit* un = svc->mem[slot].units;
+    return __atomic_load_n(&un[0].ready, __ATOMIC_ACQUIRE) == seq && (!split || __atomic_load_n(&un[1].ready, __ATOMIC_ACQUIRE) == seq);
+}
 bool intra_wait(IntraJob& ij)
 {
-    const uint32_t* ready = &ij.svc->mem[ij.slot].units[0].ready;
-    if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == ij.seq) return true;
+    if (intra_ready(ij.svc, ij.slot, ij.seq, ij.split)) return true;
     const uint64_t t0 = __builtin_ia32_rdtsc();
     uint64_t spins = 0;
     int64_t waitedNs = 0, lastNs = -1;
-    while (__atomic_load_n(ready, __ATOMIC_ACQUIRE) != ij.seq)
+    while (!intra_ready(ij.svc, ij.slot, ij.seq, ij.split))
     {
         __builtin_ia32_pause();
         if ((++spins & 255) == 0)
@@ -120,7 +152,7 @@ bool intra_wait(IntraJob& ij)
             }
         }
     }
-    IntraCounters& c = intra_counters();
+    IntraCounters& c = intra_counters(ij.family);
     c.waits.fetch_add(1, std::memory_order_relaxed);
     c.waitCycles.fetch_add(__builtin_ia32_rdtsc() - t0, std::memory_order_relaxed);
     return true;
@@ -128,16 +160,15 @@ bool intra_wait(IntraJob& ij)
 
 // the job's scope ends (served, or never asked for): the slot goes back once the device has written what it is going to write.  Nobody waits for a job
 // that was never asked for: its slot is parked (two per thread) and handed back when a later call finds its ready word set
-struct IntraParked { Service* svc; int slot; uint32_t seq; int looks; };
+struct IntraParked { Service* svc; int slot; uint32_t seq; int looks; bool split; };
 __attribute__((tls_model("initial-exec"))) thread_local IntraParked t_parked[2];
-inline bool intra_ready(Service* svc, int slot, uint32_t seq) { return __atomic_load_n(&svc->mem[slot].units[0].ready, __ATOMIC_ACQUIRE) == seq; }
 void intra_sweep()
 {
     for (IntraParked& z : t_parked)
     {
         if (!z.svc)
             continue;
-        if (intra_ready(z.svc, z.slot, z.seq)) { give_slot(z.svc, z.slot); z.svc = NULL; }
+        if (intra_ready(z.svc, z.slot, z.seq, z.split)) { give_slot(z.svc, z.slot); z.svc = NULL; }
         else if (++z.looks == 16 && x265hip_cuserve_poke(z.svc->cs, z.slot) < 0)
         {
             // a parked job that is still out after sixteen later jobs, on a service that reports a failure: it is not coming (the slot stays taken)
@@ -155,10 +186,10 @@ void intra_drop(IntraJob& ij)
     if (!ij.active)
         return;
     ij.active = false;
-    if (intra_ready(ij.svc, ij.slot, ij.seq)) { give_slot(ij.svc, ij.slot); return; }
+    if (intra_ready(ij.svc, ij.slot, ij.seq, ij.split)) { give_slot(ij.svc, ij.slot); return; }
     intra_sweep();
     for (IntraParked& z : t_parked)
-        if (!z.svc) { z.svc = ij.svc; z.slot = ij.slot; z.seq = ij.seq; z.looks = 0; return; }
+        if (!z.svc) { z.svc = ij.svc; z.slot = ij.slot; z.seq = ij.seq; z.looks = 0; z.split = ij.split; return; }
     ij.active = true;                                       // both places taken by jobs still on the device: wait for this one after all
     if (intra_wait(ij))
         give_slot(ij.svc, ij.slot);
@@ -193,13 +224,16 @@ struct IntraThreadEnd
             return;                                          // the services are closed (or failed): their slots are gone with them
         if (t_intra.active)
             intra_drop(t_intra);
+        for (IntraJob& ij : t_intraCI)
+            if (ij.active)
+                intra_drop(ij);
         for (IntraParked& z : t_parked)
         {
             if (!z.svc)
                 continue;
-            for (int spins = 0; spins < 200000 && !intra_ready(z.svc, z.slot, z.seq); spins++)     // a scan is tens of microseconds of device time
+            for (int spins = 0; spins < 200000 && !intra_ready(z.svc, z.slot, z.seq, z.split); spins++)     // a scan is tens of microseconds of device time
                 __builtin_ia32_pause();
-            if (intra_ready(z.svc, z.slot, z.seq))
+            if (intra_ready(z.svc, z.slot, z.seq, z.split))
                 give_slot(z.svc, z.slot);
             z.svc = NULL;
         }
@@ -208,7 +242,7 @@ struct IntraThreadEnd
 thread_local IntraThreadEnd t_intraThreadEnd;
 
 bool intra_slots_in(const EncoderPrimitives& p, int log2n);
-bool intra_submit(IntraJob& ij, const pixel* blob, int samples, int log2n)
+bool intra_submit(IntraJob& ij, const pixel* blob, int samples, int log2n, int family)
 {
     (void)&t_intraThreadEnd;                                 // (constructed on first use: registers the destructor with this thread)
     intra_sweep();
@@ -219,7 +253,8 @@ bool intra_submit(IntraJob& ij, const pixel* blob, int samples, int log2n)
     if (slot < 0)
         return false;
     x265hip_intrajob job;
-    job.bitDepth = X265_DEPTH; job.mark = X265HIP_INTRAJOB_MARK; job.log2Size = (uint32_t)log2n; job.reserved = 0;
+    const bool split = g_intraSplit && log2n >= 4;
+    job.bitDepth = X265_DEPTH; job.mark = X265HIP_INTRAJOB_MARK; job.log2Size = (uint32_t)log2n; job.flags = split ? X265HIP_INTRAJOB_SPLIT : 0;
     memcpy(svc->mem[slot].pixels, blob, sizeof(pixel) * samples);
     uint32_t seq = 0;
     if (x265hip_cuserve_submit_intra(svc->cs, slot, &job, &seq))
@@ -230,8 +265,9 @@ bool intra_submit(IntraJob& ij, const pixel* blob, int samples, int log2n)
         return false;
     }
     if (blob != ij.sent) memcpy(ij.sent, blob, sizeof(pixel) * samples);
-    ij.svc = svc; ij.slot = slot; ij.seq = seq; ij.log2n = log2n; ij.active = true;
-    intra_counters().jobs.fetch_add(1, std::memory_order_relaxed);
+    ij.svc = svc; ij.slot = slot; ij.seq = seq; ij.log2n = log2n; ij.split = split; ij.family = family; ij.active = true;
+    intra_counters(family).jobs.fetch_add(1, std::memory_order_relaxed);
+    if (split) intra_counters(family).split.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -240,32 +276,41 @@ void intra_unasked()
     IntraJob& ij = t_intra;
     if (ij.active)
     {
-        intra_counters().dropped.fetch_add(1, std::memory_order_relaxed);
+        intra_counters(ij.family).dropped.fetch_add(1, std::memory_order_relaxed);
         intra_drop(ij);
     }
 }
 
 // called by Search::predInterSearch's seam for the 2Nx2N candidate: will this CU be tried as intra (analysis.cpp:1595)?  Then its scan leaves now.
+// RD levels 5-6 (compressInterCU_rd5_6): the try is Search::checkIntra's (analysis.cpp:2288-2294) under the same conditions — slice type or --b-intra, not a
+// 64x64 CU, !limitReferences || splitIntra.  There the 2Nx2N inter search comes BEFORE the sub-CU recursion (Step 1, analysis.cpp:2013-2024; the intra try
+// is Step 3's last): the job is out during the whole recursion, which writes inside the CU only, so it is kept per block size (t_intraCI) and only the next
+// CU of the same size drops it; and splitIntra cannot be read from the split prediction's trace yet, so with --limit-refs every candidate CU sends a job.
+// The rectangular and AMP candidates' predInterSearch calls in between leave the job alone (the seam calls this for 2Nx2N only).
 void intra_ahead(Search* se, Mode& interMode, const CUGeom& cuGeom)
 {
-    IntraJob& ij = t_intra;
+    const int log2n = (int)cuGeom.log2CUSize;
+    const int family = se->m_param->rdLevel > 4;            // whose try it will be: checkIntraInInter's (RD 2-4) or checkIntra's (RD 5-6)
+    if (family && (log2n < 3 || log2n > 5))
+        return;
+    IntraJob& ij = family ? t_intraCI[log2n - 3] : t_intra;
     if (ij.active)
     {
-        intra_counters().dropped.fetch_add(1, std::memory_order_relaxed);
+        intra_counters(ij.family).dropped.fetch_add(1, std::memory_order_relaxed);
         intra_drop(ij);
     }
-    const int log2n = (int)cuGeom.log2CUSize;
     const Slice* slice = interMode.cu.m_slice;
     // (only sizes whose table slots are installed: a job checkIntraInInter could never adopt would only hold a slot)
-    if (!g_intraAhead || !intra_enabled() || log2n < g_intraMinLog2 || log2n > 5 || !intra_slots_in(primitives, log2n) || log2n == (int)g_log2Size[se->m_param->maxCUSize] ||
-        !(slice->m_sliceType != B_SLICE || se->m_param->bIntraInBFrames) || se->m_param->rdLevel < 2 || se->m_param->rdLevel > 4 || se->m_param->bDistributeModeAnalysis ||
+    if (!g_intraAhead || !intra_enabled() || log2n < g_intraMinLog2 || log2n > 5 || !intra_slots_in(primitives, log2n) ||
+        (family ? !g_intraCheckIntra : log2n == (int)g_log2Size[se->m_param->maxCUSize]) ||
+        !(slice->m_sliceType != B_SLICE || se->m_param->bIntraInBFrames) || se->m_param->rdLevel < 2 || se->m_param->rdLevel > 6 || se->m_param->bDistributeModeAnalysis ||
         se->m_param->analysisLoad || (se->m_param->bCTUInfo & 4))
         return;
     // With --limit-refs (preset medium and slower) the intra try needs `splitIntra` (analysis.cpp:1633): no sub-CU recursion for this CU, or a sub-CU whose
     // best mode is intra (:1182, :1353, :1369).  The recursion leaves its trace in the depth's split prediction — initSubCU to this CU (:1346), the sub-CUs'
     // data copied in quadrant by quadrant (:1370) — so the flag can be read back; a stale trace only costs a job nobody asks for, or a scan on the host.
     int likely = 1;
-    if (se->m_param->limitReferences && g_intraAheadPredict)
+    if (se->m_param->limitReferences && g_intraAheadPredict && !family)
     {
         const CUData& sp = static_cast<Analysis*>(se)->m_modeDepth[cuGeom.depth].pred[Analysis::PRED_SPLIT].cu;
         if (sp.m_cuAddr == interMode.cu.m_cuAddr && sp.m_absIdxInCTU == cuGeom.absPartIdx && sp.m_encData == interMode.cu.m_encData && cuGeom.log2CUSize > 3)
@@ -278,14 +323,14 @@ void intra_ahead(Search* se, Mode& interMode, const CUGeom& cuGeom)
     }
     if (!likely)
     {
-        intra_counters().aheadBy[0].fetch_add(1, std::memory_order_relaxed);      // (not sent: counted to show what the prediction withholds)
+        intra_counters(family).aheadBy[0].fetch_add(1, std::memory_order_relaxed);      // (not sent: counted to show what the prediction withholds)
         return;
     }
     const int samples = intra_pack(se, interMode.cu, cuGeom, *interMode.fencYuv, ij.sent);
-    if (intra_submit(ij, ij.sent, samples, log2n))
+    if (intra_submit(ij, ij.sent, samples, log2n, family))
     {
-        intra_counters().ahead.fetch_add(1, std::memory_order_relaxed);
-        intra_counters().aheadBy[1].fetch_add(1, std::memory_order_relaxed);
+        intra_counters(family).ahead.fetch_add(1, std::memory_order_relaxed);
+        intra_counters(family).aheadBy[1].fetch_add(1, std::memory_order_relaxed);
     }
 }
 
@@ -296,10 +341,12 @@ template <int CU>
 int sa8d_slot(const pixel* a, intptr_t sa, const pixel* b, intptr_t sb)
 {
     IntraCtx& c = t_ictx;
-    if (c.active && b >= c.predBuf && b < c.predBuf + 33 * c.n * c.n && (1 << (CU + 2)) == c.n)
+    if (c.active && (1 << (CU + 2)) == c.n && (c.allangs ? b >= c.predBuf && b < c.predBuf + 33 * c.n * c.n : b == c.predOne))
     {
         const int mode = c.allangs ? 2 + (int)((b - c.predBuf) / (c.n * c.n)) : c.lastMode;
         const int v = c.costs[mode];
+        if (--c.left == 0)
+            c.active = false;                                   // (the scan of estIntraPredQT is over: what follows under this context is not the scan's)
         if (c.verify)
         {
             const int want = g_prev.cu[CU].sa8d(a, sa, b, sb);
@@ -317,7 +364,7 @@ template <int CU, int MODE>
 void intra_pred_slot(pixel* dst, intptr_t dstStride, const pixel* srcPix, int dirMode, int bFilter)
 {
     IntraCtx& c = t_ictx;
-    if (c.active && dst == c.predBuf && (1 << (CU + 2)) == c.n)
+    if (c.active && dst == c.predOne && (1 << (CU + 2)) == c.n)
     {
         c.lastMode = MODE;
         c.allangs = false;
@@ -397,16 +444,16 @@ void Search::checkIntraInInter(Mode& intraMode, const CUGeom& cuGeom)
                 intra_counters().aheadHit.fetch_add(1, std::memory_order_relaxed);
             else
             {
-                intra_counters().dropped.fetch_add(1, std::memory_order_relaxed);
+                intra_counters(ij.family).dropped.fetch_add(1, std::memory_order_relaxed);
                 intra_drop(ij);
             }
         }
         if (!ij.active && log2n >= g_intraSyncMinLog2)
-            intra_submit(ij, cur, samples, log2n);
+            intra_submit(ij, cur, samples, log2n, 0);
         if (ij.active && intra_wait(ij))
         {
             IntraCtx& c = t_ictx;
-            c.active = true; c.allangs = false; c.predBuf = m_intraPredAngs; c.fencT = m_fencTransposed; c.n = 1 << log2n; c.lastMode = DC_IDX;
+            c.active = true; c.allangs = false; c.predOne = c.predBuf = m_intraPredAngs; c.fencT = m_fencTransposed; c.n = 1 << log2n; c.lastMode = DC_IDX; c.left = 1 << 30;
             c.costs = reinterpret_cast<const int32_t*>(ij.svc->mem[ij.slot].levels); c.verify = g_verify;
             if (g_time) { Timed t(13 + cuGeom.log2CUSize - 2); refCheckIntraInInter(this, intraMode, cuGeom); }
             else refCheckIntraInInter(this, intraMode, cuGeom);
@@ -419,7 +466,7 @@ void Search::checkIntraInInter(Mode& intraMode, const CUGeom& cuGeom)
     }
     else if (ij.active)
     {
-        intra_counters().dropped.fetch_add(1, std::memory_order_relaxed);
+        intra_counters(ij.family).dropped.fetch_add(1, std::memory_order_relaxed);
         intra_drop(ij);
     }
     intra_counters().host.fetch_add(1, std::memory_order_relaxed);
@@ -430,6 +477,65 @@ void Search::checkIntraInInter(Mode& intraMode, const CUGeom& cuGeom)
         return;
     }
     refCheckIntraInInter(this, intraMode, cuGeom);
+}
+
+// ---- the same scan inside Search::checkIntra -> estIntraPredQT (search.cpp:1236-1287, :1509-1629): every CU of an I slice (Analysis::compressIntraCU) and
+// the intra try of RD levels 5-6 (compressInterCU_rd5_6, analysis.cpp:2288-2303).  The same function of the same inputs — the two initAdiPattern lines and the
+// source block in, DC, planar and 33 angular predictions, cu[].sa8d of each against the source, no cost shift (a 64x64 CU is never tried) — so the job, the
+// restatement and the device code are checkIntraInInter's.  The reference's body runs (renamed to ...Body in search_seam.o: the binding defines the name
+// analysis.cpp calls) and the table slots answer its 35 sa8d calls: DC, planar and a per-mode table's angular predictions go to m_intraPred there, the
+// all-angles predictions to m_intraPredAngs.  After the 35th answer the context ends itself: codeIntraLumaQT's predictions (into predYuv) and the chroma
+// search's sa8d never touched these buffers anyway.  Mode bits, the 1.25x candidate list and the RD tries stay the reference's.
+// In an I slice nothing can leave ahead (a CU's neighbours are final only when the CU before it is coded): the thread waits the round trip, from
+// X265HIP_INTRASCAN_SYNC_MIN up.  At RD 5-6 the job was sent by predInterSearch's seam (intra_ahead) and is adopted if it compares equal.
+void Search::checkIntra(Mode& intraMode, const CUGeom& cuGeom, PartSize partSize)
+{
+    const int log2n = (int)cuGeom.log2CUSize;
+    if (partSize != SIZE_2Nx2N || log2n < 3 || log2n > 5)
+    {
+        refCheckIntra(this, intraMode, cuGeom, partSize);   // (NxN partitions, 64x64: never jobs, and no job of theirs can be out)
+        return;
+    }
+    IntraJob& ij = t_intraCI[log2n - 3];
+    if (intra_enabled() && g_intraCheckIntra && intraMode.cu.m_lumaIntraDir[0] == (uint8_t)ALL_IDX && log2n >= g_intraMinLog2 && log2n <= 5 &&
+        intra_slots_in(primitives, log2n) && !m_param->bDistributeModeAnalysis && !m_param->analysisLoad && !(m_param->bCTUInfo & 4) && !t_ictx.active)
+    {
+        pixel cur[kIntraMaxSamples];
+        const int samples = intra_pack(this, intraMode.cu, cuGeom, *intraMode.fencYuv, cur);
+        if (ij.active)
+        {
+            if (ij.log2n == log2n && !memcmp(cur, ij.sent, sizeof(pixel) * samples))
+                intra_counters(1).aheadHit.fetch_add(1, std::memory_order_relaxed);
+            else
+            {
+                intra_counters(ij.family).dropped.fetch_add(1, std::memory_order_relaxed);
+                intra_drop(ij);
+            }
+        }
+        if (!ij.active && log2n >= g_intraSyncMinLog2)
+            intra_submit(ij, cur, samples, log2n, 1);
+        if (ij.active && intra_wait(ij))
+        {
+            IntraCtx& c = t_ictx;
+            c.active = true; c.allangs = false; c.predOne = m_intraPred; c.predBuf = m_intraPredAngs; c.fencT = m_fencTransposed; c.n = 1 << log2n; c.lastMode = DC_IDX;
+            c.left = 35; c.costs = reinterpret_cast<const int32_t*>(ij.svc->mem[ij.slot].levels); c.verify = g_verify;
+            refCheckIntra(this, intraMode, cuGeom, partSize);
+            c.active = false;
+            give_slot(ij.svc, ij.slot);
+            ij.active = false;
+            intra_counters(1).served.fetch_add(1, std::memory_order_relaxed);
+            if (m_slice->isIntra()) intra_counters(1).servedI.fetch_add(1, std::memory_order_relaxed);
+            return;
+        }
+    }
+    else if (ij.active)
+    {
+        intra_counters(ij.family).dropped.fetch_add(1, std::memory_order_relaxed);
+        intra_drop(ij);
+    }
+    if (g_intraCheckIntra && log2n >= g_intraMinLog2)
+        intra_counters(1).host.fetch_add(1, std::memory_order_relaxed);
+    refCheckIntra(this, intraMode, cuGeom, partSize);
 }
 
 } // namespace X265_NS
