@@ -878,13 +878,22 @@ typedef struct x265hip_cujob
  * pixel block: the unit's source block, its prediction, then its 1 024 levels (int16, rows contiguous).  Results in units[0]: numSig (non-zero levels counted),
  * zeroDist, codedDist, codedEnergy and the unit's `resi` block; readyInv, then ready. */
 #define X265HIP_CUJOB_INVERSE 8u
-/* OR-ed into coefMode (0 or 1: the valid values are 0, 1, 16 and 17; an inverse job has nothing to denoise): noise reduction.  Behind cu[].dct every unit's
+/* OR-ed into coefMode (0 or 1: the valid values are 0, 1, 16 and 17 — and the same four with X265HIP_CUJOB_LOWPASS below; an inverse job has nothing to denoise): noise reduction.  Behind cu[].dct every unit's
  * residual coefficients pass denoiseDct (reference common/dct.cpp:744-755, called from quant.cpp:444-451) with the offset table of the unit's category —
  * a = |c|; d = a - offset[i]; c = d < 0 ? 0 : sign(c) * d — taken from the block the caller wrote at x265hip_cujob_denoise's *offsets; the quantiser (or, in
  * coefficient mode, the `levels` block) gets the denoised coefficients, the slot's absCoef array the |c| before denoise: what the reference adds to
  * residualSum[category], which the caller does for the calls it answers.  The source block's transform (sourceDct) is not denoised; zeroDist is what it was.
  * x265hip_cujob_features() bit 1. */
 #define X265HIP_CUJOB_DENOISE 16u
+/* OR-ed into coefMode like X265HIP_CUJOB_DENOISE (the valid values become 0, 1, 16, 17, 32, 33, 48, 49 and X265HIP_CUJOB_INVERSE alone: the inverse half has
+ * nothing low-pass about it): the process's cu[].dct of sizes 16 and 32 are the low-pass transforms of --lowpass-dct (reference common/lowpassdct.cpp:64-112,
+ * enabled by primitives.cpp:75-86).  Every unit of transform size n = 16 or 32, of any plane — and with sourceDct a luma unit's source block — is transformed as
+ *   sum = (int16_t)(the four samples of a 2x2 cell); avg = sum >> 2; total += sum;   coefficients = the ordinary (n / 2)-point forward DCT of avg, with ITS shifts,
+ * in the top-left quadrant of an n x n block of zeros, entry 0 replaced by (int16_t)(total >> 1) (n = 16) or (int16_t)(total >> 3) (n = 32): the cast wraps as
+ * the reference's does.  Units of size 8 keep the standard DCT.  Everything behind cu[].dct (denoise — the zeros add 0 to absCoef —, quantiser, sign hiding,
+ * dequantiser, the full n-point inverse, the distortions) is unchanged and sees the whole n x n block.  x265hip_cujob_features() bit 3; a job with the flag on a
+ * service that x265hip_cujob_lowpass was never called on is X265HIP_EINVAL at submit. */
+#define X265HIP_CUJOB_LOWPASS 32u
 typedef struct x265hip_cujob_unit
 {
     uint32_t ready;               /* == the job's ticket once this unit's numSig, zeroDist and levels are in place (the forward half) */
@@ -966,7 +975,8 @@ X265HIP_HD static inline int x265hipi_cujob_denoise_offset(const x265hip_cujob* 
 /* the chroma formats this library's CU jobs accept: bit f set for x265hip_cujob::chroma == f (0xF here).  Needs no device. */
 uint32_t x265hip_cujob_formats(void);
 /* what else this library's CU jobs can do: bit 0 = table sets of scaling lists (x265hip_cujob::scaling), bit 1 = noise reduction (X265HIP_CUJOB_DENOISE,
- * x265hip_cujob_denoise), bit 2 = intra scans split over the slot's two workgroups (X265HIP_INTRAJOB_SPLIT).  Needs no device. */
+ * x265hip_cujob_denoise), bit 2 = intra scans split over the slot's two workgroups (X265HIP_INTRAJOB_SPLIT), bit 3 = the low-pass transforms of
+ * --lowpass-dct (X265HIP_CUJOB_LOWPASS, x265hip_cujob_lowpass).  Needs no device. */
 uint32_t x265hip_cujob_features(void);
 /* A table set = the quantiser and dequantiser matrices of the inter lists a job uses, packed [size 8, 16, 32][plane Y, Cb, Cr][rem 0..5][n * n] (rows
  * contiguous: ScalingList::m_quantCoef / m_dequantCoef [1..3][3..5][0..5] as the encoder holds them, scalinglist.cpp:342-415).  quant_c multiplies in int:
@@ -1010,6 +1020,9 @@ int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, con
  * The first call on a service has its kernels replaced by the ones that hold the denoise step (a resident server leaves and starts again, as around
  * x265hip_cujob_scaling_add: once per service); a job with the flag on a service that never saw this call is X265HIP_EINVAL at submit. */
 int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef);
+/* (optional like x265hip_cujob_denoise) has the service's kernels replaced by the ones that hold the low-pass forward transforms, once per service and in the
+ * same way (a resident server leaves and starts again): from then on jobs may carry X265HIP_CUJOB_LOWPASS.  Jobs without the flag are served as before. */
+int x265hip_cujob_lowpass(x265hip_cuserve* cs);
 
 /* ---- SAO statistics of one CTU as a job of the same service (round 5) ---------------------------------------------------------------------
  * SAO::calcSaoStatsCTU (reference source/encoder/sao.cpp:735-917; called per plane from rdoSaoUnitCu :1293-1305) measures, for the deblocked CTU, the

@@ -4,7 +4,8 @@
 //                                                stamps 1: the chain's stage stamps (job.reserved, x265hip_cujob_unit::reserved) of the first luma and the first Cb unit
 //   CUSERVE_RT_SAO_DEPTH=10|12: the SAO statistics jobs at that depth (16-bit samples), one luma plane per job as the seam sends them
 //   last: the 32x32 job as a DENOISE job (X265HIP_CUJOB_DENOISE: 2.5 KB of offsets through the BAR in front of the doorbell, 3 KB of |coefficient| read back), and
-//   the plain 32x32 job once more on the service the denoise call has switched over (CUSERVE_RT_ONLY=dn: these two alone)
+//   the plain 32x32 job once more on the service the denoise call has switched over (CUSERVE_RT_ONLY=dn: these two alone); then the 32x32 job as a LOWPASS job
+//   (X265HIP_CUJOB_LOWPASS: the half-size forward transforms of --lowpass-dct; CUSERVE_RT_ONLY=lp: this one alone)
 #include <atomic>
 #include <algorithm>
 #include <chrono>
@@ -27,7 +28,7 @@ int main(int argc, char** argv)
     // CUSERVE_RT_ONLY=cu5|cu6|sao, CUSERVE_RT_THREADS=<n>: one job shape from one thread count — the counter passes (tools/exp/gpu.sh pmc) want launches of one kind
     const char* only = getenv("CUSERVE_RT_ONLY");
     const int onlyT = getenv("CUSERVE_RT_THREADS") ? atoi(getenv("CUSERVE_RT_THREADS")) : 0;
-    // dn: 0 a plain job; 1 a denoise job; 2 a plain job after the service was switched over
+    // dn: 0 a plain job; 1 a denoise job; 2 a plain job after the service was switched over; 3 a low-pass job
     auto run_cu = [&](int log2cu, int T, int dn) -> bool
         {
             std::vector<std::vector<double>> lat(T), first(T), dev(T);
@@ -49,6 +50,7 @@ int main(int argc, char** argv)
                 for (auto& o : tabs) { s = s * 1664525u + 1013904223u; o = (uint16_t)((s >> 24) & 7); }
                 tabs[0] = tabs[1024] = 0;
                 if (dn == 1 && x265hip_cujob_denoise(cs, t, &offsets, &absCoef)) { fprintf(stderr, "denoise: %s\n", x265hip_last_error()); failed = true; }
+                if (dn == 3 && x265hip_cujob_lowpass(cs)) { fprintf(stderr, "lowpass: %s\n", x265hip_last_error()); failed = true; }
                 while (!go.load()) {}
                 for (int i = 0; i < iters + 100 && !failed; i++)
                 {
@@ -62,6 +64,7 @@ int main(int argc, char** argv)
                         job->coefMode = X265HIP_CUJOB_DENOISE;
                         memcpy(offsets, tabs.data(), tabs.size() * sizeof(uint16_t));
                     }
+                    if (dn == 3) job->coefMode = X265HIP_CUJOB_LOWPASS;
                     memcpy(pixels, src.data(), bytes);
                     uint32_t seq = 0;
                     if (x265hip_cuserve_submit(cs, t, &seq)) { fprintf(stderr, "submit: %s\n", x265hip_last_error()); failed = true; break; }
@@ -123,7 +126,7 @@ int main(int argc, char** argv)
             std::sort(all.begin(), all.end()); std::sort(f.begin(), f.end());
             double sum = 0; for (double x : all) sum += x;
             printf("%s, %dx%d CU (4:2:0, 8 bit, 32x32 transforms%s), %2d thread%s: whole job mean %6.1f us, median %6.1f, p99 %6.1f; first luma unit forward half median %6.1f us (%4.1f us of it on the device, doorbell seen -> ready word issued); %.0f jobs/s in total\n",
-                   mode ? "one launch per job" : "resident server   ", 1 << log2cu, 1 << log2cu, dn == 1 ? ", DENOISE job" : dn == 2 ? ", plain job after the denoise call" : "", T, T > 1 ? "s" : " ",
+                   mode ? "one launch per job" : "resident server   ", 1 << log2cu, 1 << log2cu, dn == 1 ? ", DENOISE job" : dn == 2 ? ", plain job after the denoise call" : dn == 3 ? ", LOWPASS job" : "", T, T > 1 ? "s" : " ",
                    sum / all.size(), all[all.size() / 2],
                    all[(size_t)(all.size() * 0.99)], f[f.size() / 2], dv[dv.size() / 2], (double)T * (iters + 100) / (wall * 1e-6));
             if (stamps)
@@ -285,6 +288,11 @@ int main(int argc, char** argv)
             if ((only && only[0] != 'd') || (onlyT && T != onlyT)) continue;
             if (!run_cu(5, T, dn)) { x265hip_cuserve_close(cs); return 1; }
         }
+    for (int T : { 1, 4, 16 })
+    {
+        if ((only && only[0] != 'l') || (onlyT && T != onlyT)) continue;
+        if (!run_cu(5, T, 3)) { x265hip_cuserve_close(cs); return 1; }
+    }
     uint64_t jobs = 0, starts = 0, ns = 0;
     x265hip_cuserve_stats(cs, &jobs, &starts, &ns);
     printf("%llu jobs, %llu server starts, %.1f us of device time per job\n", (unsigned long long)jobs, (unsigned long long)starts, jobs ? ns * 1e-3 / jobs : 0.0);

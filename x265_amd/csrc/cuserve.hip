@@ -161,7 +161,8 @@ static_assert((128 + kSaoPixelBytes + 511) / 512 < 56, "SAO statistics job: the 
 // qTab / dqTab: the unit's (size, plane, rem) matrices of the job's table set (x265hip_cujob::scaling), n * n int32 each, rows contiguous; null: the flat quantiser.
 // per: the plane's qpParam.per, which dequant_scaling takes apart from the matrix
 // nrTab: a denoise job's offset table of the unit's category (n * n uint16 of the slot's offset block, rows contiguous); null: no denoise
-struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal, per; const int32_t* qTab; const int32_t* dqTab; const uint16_t* nrTab; };
+// lp: the units of this size are transformed by the low-pass forms (a job with X265HIP_CUJOB_LOWPASS, sizes 16 and 32; only the *_sets kernels look at it)
+struct PlaneParams { int qBits, add, quantScale, dqScale, dqShift, s1f, s2f, s1i, s2i, maxVal, per; const int32_t* qTab; const int32_t* dqTab; const uint16_t* nrTab; int lp; };
 
 // A table set in device memory: X265HIP_CUJOB_SCALING_ENTRIES quantiser entries, then as many dequantiser entries; [size 8, 16, 32][plane][rem][n * n]
 constexpr int kSetInts = 2 * X265HIP_CUJOB_SCALING_ENTRIES;
@@ -216,6 +217,7 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
     p.per = j.qpPer[plane];
     p.qTab = p.dqTab = nullptr;
     p.nrTab = nullptr;
+    p.lp = 0;
     if (j.scaling && sets)
     {
         // (x265hip_cuserve_submit has looked at the id and at rem: the offsets stay inside the set)
@@ -225,6 +227,54 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
     return p;
 }
 
+// ---- the low-pass forward transforms of --lowpass-dct (reference lowpassdct.cpp:64-112; X265HIP_CUJOB_LOWPASS) -------------------------------------------
+// An n x n unit (n = 16, 32) is averaged over 2x2 cells — sum = (int16_t)(four samples), avg = sum >> 2, total += sum —, the ordinary (n / 2)-point forward
+// transform of the averages (ITS shifts: one less than the n-point passes' in both) lands in the top-left quadrant of an n x n block of zeros, and entry 0 is
+// replaced by (int16_t)(total >> 1) (n = 16) or (int16_t)(total >> 3) (n = 32): the cast wraps as the reference's does (a Main10 source block brighter than 255
+// in the mean already does).  The forms exist in the DN instantiations only, which are the *_sets kernels'; everything behind the transform runs as it did.
+__device__ __forceinline__ int cell_sum(const int16_t* p, int stride)
+{
+    const uint32_t w0 = ld_unaligned<uint32_t>(p), w1 = ld_unaligned<uint32_t>(p + stride);
+    return (int)(int16_t)((int)(int16_t)(w0 & 0xffffu) + (int)(int16_t)(w0 >> 16) + (int)(int16_t)(w1 & 0xffffu) + (int)(int16_t)(w1 >> 16));
+}
+// a wave's tile (tile_chain): the residuals of the tile's G units of size N are in t.a; their low-pass coefficients replace them.  The G averaged blocks are 256
+// entries whatever N is — four per lane, and a unit's lanes are the quantiser's (lane / LPT) — and lie in t.b as the first G units of an (N / 2)-point tile, so the
+// passes are mfma_pass<N / 2> with the operand the kernel holds for that size (the tile's other units are stale LDS: every unit is transformed on its own)
+template <int N>
+__device__ __forceinline__ void lowpass_tile(TileLds& t, const BOperand& oH, int lane, int s1, int s2)
+{
+    constexpr int H = N / 2, LPT = N * N / 16;
+    const int q = lane * 4, g = q / (H * H), i = (q % (H * H)) / H, j0 = q % H;
+    const int16_t* cell = t.a + g * N * N + 2 * i * N + 2 * j0;
+    int avg[4], total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const int sum = cell_sum(cell + 2 * k, N);
+        avg[k] = sum >> 2;
+        total += sum;
+    }
+    store4(t.b + q, avg);
+    total = group_sum(total, LPT);
+    const v4i bH = { oH.b[0], oH.b[1], oH.b[2], oH.b[3] };
+    mfma_pass<H, false>(t.b, t.c, lane, bH, oH.corr, s1);
+    mfma_pass<H, false>(t.c, t.b, lane, bH, oH.corr, s2);
+#pragma unroll
+    for (int half = 0; half < 2; half++)
+    {
+        const int e = lane * 16 + half * 8;
+        const int rr = (e % (N * N)) / N, cc = e % N;
+        int v[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        if (rr < H && cc < H)
+        {
+            const int16_t* c = t.b + (e / (N * N)) * H * H + rr * H + cc;
+            load4(c, v); load4(c + 4, v + 4);
+        }
+        if (rr == 0 && cc == 0) v[0] = (int)(int16_t)(total >> (N == 16 ? 1 : 3));
+        store4(t.a + e, v); store4(t.a + e + 4, v + 4);
+    }
+}
+
 // One tile: units u0 .. u0 + G - 1 (G = (32 / N)^2, raster order, `count` of them exist) of size N x N of one plane.
 //   src / prd: the plane's source and prediction in LDS, `pw` elements per row; the plane has pw / N units per row (as many rows of them as the caller counts:
 //   pw / N, twice that for a 4:2:2 chroma plane)
@@ -232,9 +282,10 @@ __device__ __forceinline__ PlaneParams plane_params(const x265hip_cujob& j, int 
 // 16-byte loads, issued ahead of the stage in front of the one that needs them); the flat instantiation is the code it was
 // DN: the kernel serves denoise jobs (the *_sets pair): when the job is one (qp.nrTab, uniform over the workgroup), denoiseDct between the forward transform and
 // the quantiser with the offsets qp.nrTab (a lane's 16 are 32 contiguous bytes); |c| goes out in absCoef.  (One instantiation for both kinds of job: a kernel
-// that held the chains twice kept some of sign hiding's level arrays in scratch.)
+// that held the chains twice kept some of sign hiding's level arrays in scratch.)  The same holds for a low-pass job (qp.lp): lowpass_tile in place of the two
+// forward passes, with bopH, the forward operand of size N / 2.
 template <typename P, int N, bool SC, bool DN>
-__device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64], const P* src, const P* prd, int pw, int u0, int count, const PlaneParams qp,
+__device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64], [[maybe_unused]] const BOperand (*bopH)[64], const P* src, const P* prd, int pw, int u0, int count, const PlaneParams qp,
                                            bool signHide, x265hip_cujob_unit* units, int unitBase, int16_t* levels, int16_t* resi, int elemBase, uint32_t seq, uint64_t t0, bool stamps,
                                            int coef, [[maybe_unused]] uint16_t* absCoef)
 {
@@ -295,9 +346,18 @@ __device__ __forceinline__ void tile_chain(TileLds& t, const BOperand (*bop)[64]
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     // ---- forward transform: a -> b -> a
-    mfma_pass<N, false>(t.a, t.b, lane, bF, corrF, qp.s1f);
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    mfma_pass<N, false>(t.b, t.a, lane, bF, corrF, qp.s2f);
+    bool lowpass = false;
+    if constexpr (DN && N >= 16) lowpass = qp.lp != 0;
+    if (lowpass)
+    {
+        if constexpr (DN && N >= 16) lowpass_tile<N>(t, bopH[0][lane], lane, qp.s1f - 1, qp.s2f - 1);
+    }
+    else
+    {
+        mfma_pass<N, false>(t.a, t.b, lane, bF, corrF, qp.s1f);
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        mfma_pass<N, false>(t.b, t.a, lane, bF, corrF, qp.s2f);
+    }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     if constexpr (DN)
     {
@@ -776,6 +836,10 @@ __device__ __forceinline__ void team_inverse32(TileLds& t, TeamLds& tm, const P*
     team_barrier();                              // (the tile and the team's words are free for the next unit)
 }
 
+// (below: the low-pass form's passes; OS: the row stride of a forward pass's output block)
+template <bool INV, int OS = 16>
+__device__ __forceinline__ void solo_pass16(const int16_t* in, int16_t* out, int lane, const TeamOperand& op, int shift);
+
 // unit `u` (raster order; `pw` elements per row of the plane in LDS) of a plane whose transform size is 32: tile_chain<P, 32>'s work for one unit
 // DN: every thread denoises its four coefficients behind the forward transform; their |c| meet in `absLds` (a tile no team unit uses) and leave through wave 0
 // with the levels
@@ -803,6 +867,8 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
         const uint2 n0 = *reinterpret_cast<const uint2*>(qp.nrTab + e);
         nr[0] = n0.x; nr[1] = n0.y;
     }
+    bool lowpass = false;
+    if constexpr (DN) lowpass = qp.lp != 0;
     int fv[4], pv[4];
     {
         const int off = (uy * 32 + (e >> 5)) * pw + ux * 32 + (e & 31);
@@ -811,7 +877,20 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
         int r[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) r[i] = srcOnly ? fv[i] : fv[i] - pv[i];
-        store4(t.a + e, r);
+        if (!lowpass)
+            store4(t.a + e, r);
+        else
+        {
+            // the low-pass form (lowpass_tile), out of the registers: a thread's four samples are the upper or lower halves of two 2x2 cells, whose other halves
+            // the thread one row below / above holds (tid ^ 8, the same wave).  The thread of the even row finishes the left cell, the one of the odd row the right
+            // cell: 256 averaged entries, one per thread, in t.b as a 16x16 unit; the sums meet through team_part / team_total
+            const int h0 = r[0] + r[1], h1 = r[2] + r[3];
+            const int o0 = __shfl_xor(h0, 8, kWave), o1 = __shfl_xor(h1, 8, kWave);
+            const int odd = (tid >> 3) & 1;
+            const int sum = (int)(int16_t)(odd ? h1 + o1 : h0 + o0);
+            st_unaligned<int16_t>(t.b + (tid >> 4) * 16 + 2 * (tid & 7) + odd, (int16_t)(sum >> 2));
+            team_part(tm.part, tid, (uint32_t)sum);
+        }
     }
     uint32_t zeroP = 0;
 #pragma unroll
@@ -819,9 +898,32 @@ __device__ __forceinline__ void team_chain32(TileLds& t, TeamLds& tm, const P* s
     team_part(tm.part2, tid, zeroP);             // (read after the barriers below; nothing else writes part2 before the forward half is published)
     team_barrier();
     // ---- forward transform: a -> b -> a
-    team_pass<false>(t.a, t.b, tid, oF, qp.s1f);
-    team_barrier();
-    team_pass<false>(t.b, t.a, tid, oF, qp.s2f);
+    if (lowpass)
+    {
+        // the two 16-point passes are one wave's work (solo_pass16 with the operand of the 16x16 units), the second one writing rows of 32 into the top-left
+        // quadrant of t.a, entry 0 replaced behind it; the other three waves write the zeros of the other three quadrants meanwhile (192 threads, four entries
+        // each: 64 groups right of the quadrant, 128 below it).  Two barriers where the two team passes have three
+        if (wv == 0)
+        {
+            solo_pass16<false>(t.b, t.c, lane, tm.op16[0][lane], qp.s1f - 1);
+            solo_pass16<false, 32>(t.c, t.a, lane, tm.op16[0][lane], qp.s2f - 1);
+            // (the partial sums are two's complement words: the low 32 bits are the signed total)
+            if (lane == 0) st_unaligned<int16_t>(t.a, (int16_t)((int)(uint32_t)team_total(tm.part) >> 3));
+        }
+        else
+        {
+            const int k = tid - 64;
+            const int z = k < 64 ? (k >> 2) * 32 + 16 + (k & 3) * 4 : 512 + (k - 64) * 4;
+            const int zero[4] = { 0, 0, 0, 0 };
+            store4(t.a + z, zero);
+        }
+    }
+    else
+    {
+        team_pass<false>(t.a, t.b, tid, oF, qp.s1f);
+        team_barrier();
+        team_pass<false>(t.b, t.a, tid, oF, qp.s2f);
+    }
     team_barrier();
     if constexpr (DN)
     {
@@ -1068,7 +1170,7 @@ __device__ __forceinline__ void make_solo16_operand(int lane, TeamOperand& o)
     o.corr = 128 * sum;
     o.pad = 0;
 }
-template <bool INV>
+template <bool INV, int OS>
 __device__ __forceinline__ void solo_pass16(const int16_t* in, int16_t* out, int lane, const TeamOperand& op, int shift)
 {
     const int i = lane & 15, k0 = 8 * (lane >> 4);
@@ -1107,7 +1209,7 @@ __device__ __forceinline__ void solo_pass16(const int16_t* in, int16_t* out, int
         v[e] = INV ? clip3i(-32768, 32767, t) : t;
     }
     if (!INV)
-        store4(out + n * 16 + row0, v);
+        store4(out + n * OS + row0, v);
     else
     {
 #pragma unroll
@@ -1123,8 +1225,9 @@ __device__ __forceinline__ unsigned long long solo_total(uint32_t v)
            (uint32_t)__builtin_amdgcn_readlane((int)r, 32) + (uint32_t)__builtin_amdgcn_readlane((int)r, 48);
 }
 
+// bop8 (DN): the forward operand of the 8-point passes, for a low-pass job (lowpass_tile: one averaged entry per lane)
 template <typename P, bool SC, bool DN>
-__device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)[64], const P* src, const P* prd, const PlaneParams qp, bool signHide,
+__device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)[64], [[maybe_unused]] const BOperand (*bop8)[64], const P* src, const P* prd, const PlaneParams qp, bool signHide,
                                              x265hip_cujob_unit* un, int16_t* levels, int16_t* resi, uint32_t seq, uint64_t t0, bool stamps, int coef,
                                              [[maybe_unused]] uint16_t* absCoef)
 {
@@ -1156,8 +1259,28 @@ __device__ __forceinline__ void solo_chain16(TileLds& t, const TeamOperand (*op)
     for (int i = 0; i < 4; i++) { const int d0 = fv[i] - pv[i]; zeroP += (uint32_t)(d0 * d0); }
     const unsigned long long zero = solo_total(zeroP);
     // ---- forward transform: a -> b -> a
-    solo_pass16<false>(t.a, t.b, lane, oF, qp.s1f);
-    solo_pass16<false>(t.b, t.a, lane, oF, qp.s2f);
+    bool lowpass = false;
+    if constexpr (DN) lowpass = qp.lp != 0;
+    if (lowpass)
+    {
+        const BOperand& o8 = bop8[0][lane];
+        const v4i b8 = { o8.b[0], o8.b[1], o8.b[2], o8.b[3] };
+        const int sum = cell_sum(t.a + 2 * (lane >> 3) * 16 + 2 * (lane & 7), 16);
+        st_unaligned<int16_t>(t.b + lane, (int16_t)(sum >> 2));
+        const int total = wave_sum(sum);
+        mfma_pass<8, false>(t.b, t.c, lane, b8, o8.corr, qp.s1f - 1);
+        mfma_pass<8, false>(t.c, t.b, lane, b8, o8.corr, qp.s2f - 1);
+        const int rr = e >> 4, cc = e & 15;
+        int v[4] = { 0, 0, 0, 0 };
+        if (rr < 8 && cc < 8) load4(t.b + rr * 8 + cc, v);
+        if (lane == 0) v[0] = (int)(int16_t)(total >> 1);
+        store4(t.a + e, v);
+    }
+    else
+    {
+        solo_pass16<false>(t.a, t.b, lane, oF, qp.s1f);
+        solo_pass16<false>(t.b, t.a, lane, oF, qp.s2f);
+    }
     if constexpr (DN) if (dn)
     {
         // ---- denoiseDct (tile_chain): a lane's own four coefficients, in place; |c| out
@@ -1451,8 +1574,9 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
     const P* src = reinterpret_cast<const P*>(L.pix);
     const P* prd = src + planeElems;
     // (the flag is masked where it can be set: the other kernels are never given a job with it, x265hip_cuserve_submit)
-    const uint32_t coefMode = DN ? j.coefMode & ~X265HIP_CUJOB_DENOISE : j.coefMode;
+    const uint32_t coefMode = DN ? j.coefMode & ~(X265HIP_CUJOB_DENOISE | X265HIP_CUJOB_LOWPASS) : j.coefMode;
     [[maybe_unused]] const bool denoiseJob = DN && (j.coefMode & X265HIP_CUJOB_DENOISE) != 0;
+    [[maybe_unused]] const bool lowpassJob = DN && (j.coefMode & X265HIP_CUJOB_LOWPASS) != 0;
     if (coefMode == X265HIP_CUJOB_INVERSE)
     {
         if (role == 0) team_inverse_job<P, SC>(s, L, seq, t0, sets);
@@ -1477,6 +1601,7 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
             const int pw = plane ? NC : N;
             PlaneParams qp = plane_params(j, plane, log2n, SC ? sets : nullptr);
             if constexpr (DN) if (denoiseJob) qp.nrTab = nrBlock + x265hipi_cujob_denoise_offset(&j, sHi, sLo, sz, plane);
+            if constexpr (DN) qp.lp = lowpassJob && log2n >= 4;
             // coefficient mode: a luma tile whose source block is wanted as well is TWO work items (residual part, source part)
             const int parts = coefMode && j.sourceDct && plane == 0 ? 2 : 1;
             const int unitBase = x265hipi_cujob_unit_index(&j, sHi, sz, plane, 0, 0);
@@ -1499,12 +1624,12 @@ __device__ __forceinline__ void run_tiles(SlotOut* s, JobLds& L, uint32_t seq, u
                 const int k = kk / parts;
                 const int coef = !coefMode ? 0 : parts == 1 ? 1 : (kk % parts) == 0 ? 1 | 4 : 2 | 4;
                 const int u0 = k * G, count = nUnits - u0 < G ? nUnits - u0 : G;
-                if (log2n == 5) tile_chain<P, 32, SC, DN>(L.tile[wv], L.bop[2], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
+                if (log2n == 5) tile_chain<P, 32, SC, DN>(L.tile[wv], L.bop[2], L.bop[1], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
                 else if (log2n == 4 && nUnits == 1 && plane && team)
                     // (the chroma units of a 32x32 CU: one 16x16 unit per plane, the wave's only work)
-                    solo_chain16<P, SC, DN>(L.tile[wv], L.team.op16, ps, pp, qp, j.signHide != 0, s->units + unitBase, s->levels + elemBase, s->resi + elemBase, seq, t0, j.reserved != 0, coef, s->absCoef + elemBase);
-                else if (log2n == 4) tile_chain<P, 16, SC, DN>(L.tile[wv], L.bop[1], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
-                else tile_chain<P, 8, SC, DN>(L.tile[wv], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
+                    solo_chain16<P, SC, DN>(L.tile[wv], L.team.op16, L.bop[0], ps, pp, qp, j.signHide != 0, s->units + unitBase, s->levels + elemBase, s->resi + elemBase, seq, t0, j.reserved != 0, coef, s->absCoef + elemBase);
+                else if (log2n == 4) tile_chain<P, 16, SC, DN>(L.tile[wv], L.bop[1], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
+                else tile_chain<P, 8, SC, DN>(L.tile[wv], L.bop[0], L.bop[0], ps, pp, pw, u0, count, qp, j.signHide != 0, s->units, unitBase, s->levels, s->resi, elemBase, seq, t0, j.reserved != 0, coef, s->absCoef);
             }
         }
     }
@@ -2055,6 +2180,7 @@ struct x265hip_cuserve
     std::atomic<uint32_t> nsets{ 0 };             // sets registered: ids 1 .. nsets are valid in x265hip_cujob::scaling
     std::mutex setLock;
     std::atomic<bool> denoise{ false };           // x265hip_cujob_denoise was called: the *_sets kernels serve (they hold the denoise step), jobs may carry the flag
+    std::atomic<bool> lowpass{ false };           // x265hip_cujob_lowpass was called: the *_sets kernels serve (they hold the low-pass transforms), jobs may carry the flag
     uint64_t idleUs = 2000;
 };
 static std::mutex g_openLock;
@@ -2066,6 +2192,12 @@ static bool team_off()
 {
     static const bool off = getenv("X265HIP_CUSERVE_TEAM") && !atoi(getenv("X265HIP_CUSERVE_TEAM"));
     return off;
+}
+
+// the service is served by the *_sets kernels: a table set is registered, or denoise / low-pass jobs were announced
+static bool sets_kernels(const x265hip_cuserve* cs)
+{
+    return cs->sets || cs->denoise.load(std::memory_order_acquire) || cs->lowpass.load(std::memory_order_acquire);
 }
 
 static int start_server(x265hip_cuserve* cs)
@@ -2085,7 +2217,7 @@ static int start_server(x265hip_cuserve* cs)
     if (e == hipSuccess)
     {
         const uint64_t idle = cs->idleUs * 100 | (getenv("X265HIP_CUSERVE_SPIN") && atoi(getenv("X265HIP_CUSERVE_SPIN")) ? 1ull << 63 : 0ull) | (team_off() ? 1ull << 62 : 0ull);
-        if (cs->sets || cs->denoise.load(std::memory_order_acquire))
+        if (sets_kernels(cs))
             hipLaunchKernelGGL(cu_server_kernel_sets, dim3(2 * cs->slots), dim3(256), 0, cs->serverStream, cs->inDev, cs->outDev, cs->devHostCtl, cs->ctl, gen ? gen : 1u, idle,
                                (const int32_t*)cs->sets);
         else
@@ -2325,14 +2457,17 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
     if (j.log2CUSize < 4 || j.log2CUSize > 6 || x265hipi_cujob_levels(&j, &sHi, &sLo) < 1 || !valid_depth((int)j.bitDepth) || j.chroma > 3)
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: CU 2^%u, transform sizes 2^%u..2^%u, depth %u, chroma format %u", j.log2CUSize, j.log2TrMin, j.log2TrMax,
                          j.bitDepth, j.chroma);
-    // the mode word: coefficient mode or not, with or without denoise, or an inverse job (which has nothing to denoise); denoise only on a service whose
-    // kernels hold the step (x265hip_cujob_denoise)
-    const uint32_t plainMode = j.coefMode & ~X265HIP_CUJOB_DENOISE;
+    // the mode word: coefficient mode or not, with or without denoise, with or without the low-pass transforms, or an inverse job (which has nothing to denoise
+    // and nothing low-pass about it); denoise and low-pass only on a service whose kernels hold the step (x265hip_cujob_denoise, x265hip_cujob_lowpass)
+    const uint32_t plainMode = j.coefMode & ~(X265HIP_CUJOB_DENOISE | X265HIP_CUJOB_LOWPASS);
     const bool denoiseJob = (j.coefMode & X265HIP_CUJOB_DENOISE) != 0;
+    const bool lowpassJob = (j.coefMode & X265HIP_CUJOB_LOWPASS) != 0;
     if (plainMode > 1 && !(j.coefMode == X265HIP_CUJOB_INVERSE))
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: coefMode %u", j.coefMode);
     if (denoiseJob && !cs->denoise.load(std::memory_order_acquire))
         return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: a denoise job on a service that x265hip_cujob_denoise was never called on");
+    if (lowpassJob && !cs->lowpass.load(std::memory_order_acquire))
+        return set_error(X265HIP_EINVAL, "x265hip_cuserve_submit: a low-pass job on a service that x265hip_cujob_lowpass was never called on");
     // a table set: one that is registered, and quantiser parameters that stay inside its matrices (rem picks the matrix, per is a shift count)
     if (j.scaling)
     {
@@ -2367,7 +2502,7 @@ int x265hip_cuserve_submit(x265hip_cuserve* cs, int slot, uint32_t* seqOut)
         int cur = -1;
         (void)hipGetDevice(&cur);
         if (cur != cs->device) (void)hipSetDevice(cs->device);
-        if (cs->sets || cs->denoise.load(std::memory_order_acquire))
+        if (sets_kernels(cs))
             hipLaunchKernelGGL(cu_job_kernel_sets, dim3(2), dim3(256), 0, cs->jobStreams[slot], cs->inDev + slot, cs->outDev + slot, seq, &cs->ctl->busyTicks[2 * slot],
                                team_off() ? 0u : 1u, (const int32_t*)cs->sets);
         else
@@ -2391,7 +2526,38 @@ uint32_t x265hip_cujob_formats(void)
 
 uint32_t x265hip_cujob_features(void)
 {
-    return 1u | 2u | 4u;                                      // bit 0: table sets of scaling lists (x265hip_cujob::scaling); bit 1: X265HIP_CUJOB_DENOISE; bit 2: X265HIP_INTRAJOB_SPLIT
+    // bit 0: table sets of scaling lists (x265hip_cujob::scaling); bit 1: X265HIP_CUJOB_DENOISE; bit 2: X265HIP_INTRAJOB_SPLIT; bit 3: X265HIP_CUJOB_LOWPASS
+    return 1u | 2u | 4u | 8u;
+}
+
+// once per service: the *_sets kernels take over for the step `flag` stands for.  A resident server leaves (jobs in progress are finished, waiters see
+// x265hip_cuserve_poke == 1) and whoever submits next starts the other kernel — the pause of x265hip_cujob_scaling_add, without a copy
+static int switch_kernels(x265hip_cuserve* cs, std::atomic<bool>& flag, const char* who)
+{
+    std::lock_guard<std::mutex> g(cs->setLock);
+    if (flag.load())
+        return X265HIP_OK;
+    servers_pause();
+    int e = X265HIP_OK;
+    if (cs->mode == 0)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        while (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(10))
+            __builtin_ia32_pause();
+        if (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0)
+            e = set_error(X265HIP_EHIP, "%s: the resident server did not leave", who);
+    }
+    if (!e) flag.store(true, std::memory_order_release);
+    servers_resume();
+    return e;
+}
+
+int x265hip_cujob_lowpass(x265hip_cuserve* cs)
+{
+    if (!cs) return set_error(X265HIP_EINVAL, "x265hip_cujob_lowpass: null");
+    if (!cs->lowpass.load(std::memory_order_acquire))
+        return switch_kernels(cs, cs->lowpass, "x265hip_cujob_lowpass");
+    return X265HIP_OK;
 }
 
 int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef)
@@ -2399,25 +2565,9 @@ int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, con
     if (!cs || slot < 0 || slot >= cs->slots) return set_error(X265HIP_EINVAL, "x265hip_cujob_denoise: slot %d", slot);
     if (!cs->denoise.load(std::memory_order_acquire))
     {
-        // once per service: the kernels that hold the denoise step take over.  A resident server leaves (jobs in progress are finished, waiters see
-        // x265hip_cuserve_poke == 1) and whoever submits next starts the other kernel — the pause of x265hip_cujob_scaling_add, without a copy
-        std::lock_guard<std::mutex> g(cs->setLock);
-        if (!cs->denoise.load())
-        {
-            servers_pause();
-            int e = X265HIP_OK;
-            if (cs->mode == 0)
-            {
-                const auto t0 = std::chrono::steady_clock::now();
-                while (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(10))
-                    __builtin_ia32_pause();
-                if (__atomic_load_n(&cs->hostCtl->serverState, __ATOMIC_ACQUIRE) != 0)
-                    e = set_error(X265HIP_EHIP, "x265hip_cujob_denoise: the resident server did not leave");
-            }
-            if (!e) cs->denoise.store(true, std::memory_order_release);
-            servers_resume();
-            if (e) return e;
-        }
+        // once per service: the kernels that hold the denoise step take over
+        const int e = switch_kernels(cs, cs->denoise, "x265hip_cujob_denoise");
+        if (e) return e;
     }
     if (offsets) *offsets = cs->in[slot].offsets;
     if (absCoef) *absCoef = cs->out[slot].absCoef;

@@ -196,6 +196,7 @@ PROTOTYPES = {
     "x265hip_cujob_features": (u32, []),
     "x265hip_cujob_scaling_add": (i32, [vp, vp, vp, C.POINTER(u32)]),
     "x265hip_cujob_denoise": (i32, [vp, i32, C.POINTER(vp), C.POINTER(vp)]),
+    "x265hip_cujob_lowpass": (i32, [vp]),
     "x265hip_cuserve_submit_intra": (i32, [vp, i32, vp, vp]),
     "x265hip_cuserve_stats": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     "x265hip_device_time": (i32, [i32, vp, vp, vp]),
@@ -303,6 +304,7 @@ CUJOB_PIXEL_BYTES = 2 * 12288 * 2
 CUJOB_INVERSE = 8                 # x265hip_cujob::coefMode: an inverse job
 CUJOB_DENOISE = 16                # OR-ed into x265hip_cujob::coefMode: noise reduction with the offsets of x265hip_cujob_denoise's block
 CUJOB_DENOISE_ENTRIES = 2 * (1024 + 256)
+CUJOB_LOWPASS = 32                # OR-ed into x265hip_cujob::coefMode: the low-pass forward transforms of --lowpass-dct (x265hip_cujob_lowpass)
 
 
 class LaSearch(C.Structure):

@@ -55,6 +55,11 @@ int g_denoise = 0;               // X265HIP_CUSERVE_DENOISE=1: CUs of an encode 
                                  // MI355X box, 1080p preset medium --nr-inter 400 at the bench's thread arguments, 4 interleaved rounds, byte-identical (profiles/r08_v1_cujob_denoise_ab.txt):
                                  // 8 bit 40.2 against 38.3 fps (25.7 against 27.6 CPU-s), Main10 34.2 against 32.0 (29.4 against 32.5 CPU-s) — ahead in the mean of both, but by
                                  // less than the off leg's own rounds span (37.1-40.4, 30.6-33.5), which is the bar for a default
+int g_lowpass = X265_DEPTH == 10 ? 1 : 0;       // X265HIP_CUSERVE_LOWPASS=0 / 1: CUs of a process whose transform table holds the low-pass transforms (--lowpass-dct) stay on the host / are
+                                 // handed over as jobs with X265HIP_CUJOB_LOWPASS.  Measured on the MI355X box, 1080p preset medium --lowpass-dct at the bench's thread arguments, 4
+                                 // interleaved rounds, byte-identical (profiles/r11_v1_cujob_lowpass_ab.txt): 8 bit 49.4 against 48.6 fps (21.1 against 21.0 CPU-s) — less than the
+                                 // off leg's own rounds span (46.2-50.3), the bar for a default: off; Main10 41.2 against 38.7 fps (26.8 against 28.5 CPU-s), span 37.9-39.2: on.
+                                 // Main12 was not measured: off.  Off, such encodes keep their CUs on the host and the reference's bytes
 int g_formats = 1;               // X265HIP_CUSERVE_FORMATS=0: CUs of 4:2:2 / 4:4:4 pictures are not handed over (what the binding did before their jobs existed)
 int g_slots = 64;                // X265HIP_CUSERVE_SLOTS: jobs that can be in flight (default: twice the CPUs this process may use, 16..64)
 bool g_verify = false;           // X265HIP_VERIFY=1: every served unit is recomputed by the reference's function and compared
@@ -69,7 +74,7 @@ std::atomic<bool> g_dead(false); // the device failed once: every later CU is co
 std::atomic<uint64_t> g_cycles[18][2], g_calls[18][2];
 __attribute__((tls_model("initial-exec"))) thread_local int t_inRqt = 0;
 
-struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs, scalingJobs, scalingKept, denoiseJobs, denoiseKept; };
+struct alignas(64) Counters { std::atomic<uint64_t> jobs, fwd, inv, fwdMiss, invMiss, waitCycles, waits, skipped, dist, psyHit, psyAhead, psyCoded, deadSub, deadAdd, lateSub, lateAdd, siteWaits[6], siteCycles[6], lumaHist[24], spec, specHit, psySkip, specInter, specInterHit, invJobs, invDropped, formatJobs, scalingJobs, scalingKept, denoiseJobs, denoiseKept, lowpassJobs, lowpassKept; };
 Counters g_count[64];
 std::atomic<int> g_nextShard(0);
 __attribute__((tls_model("initial-exec"))) thread_local int t_shard = -1;
@@ -241,6 +246,12 @@ void report()
             fprintf(stderr, "x265hip: cuserve: noise reduction: %llu jobs carried offsets, %llu CUs kept on the host because of their tables\n", (unsigned long long)dj,
                     (unsigned long long)dk);
     }
+    {
+        uint64_t lj = 0, lk = 0;
+        for (int i = 0; i < 64; i++) { lj += g_count[i].lowpassJobs; lk += g_count[i].lowpassKept; }
+        if (lj || lk)
+            fprintf(stderr, "x265hip: cuserve: lowpass dct: %llu jobs carried the flag, %llu CUs kept on the host because of it\n", (unsigned long long)lj, (unsigned long long)lk);
+    }
     if (dsb || dad)
         fprintf(stderr, "x265hip: cuserve: %llu sub_ps and %llu add_ps calls of those CUs put off because only the job's answers read their results (%llu + %llu run after all)\n",
                 (unsigned long long)dsb, (unsigned long long)dad, (unsigned long long)lsb, (unsigned long long)lad);
@@ -266,6 +277,7 @@ bool decide()
         if (getenv("X265HIP_CUSERVE_INVERSE")) g_invJobs = atoi(getenv("X265HIP_CUSERVE_INVERSE")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_FORMATS")) g_formats = atoi(getenv("X265HIP_CUSERVE_FORMATS")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_DENOISE")) g_denoise = atoi(getenv("X265HIP_CUSERVE_DENOISE")) ? 1 : 0;
+        if (getenv("X265HIP_CUSERVE_LOWPASS")) g_lowpass = atoi(getenv("X265HIP_CUSERVE_LOWPASS")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_SCALING")) g_scaling = atoi(getenv("X265HIP_CUSERVE_SCALING")) ? 1 : 0;
         if (getenv("X265HIP_CUSERVE_TIMEOUT_MS") && atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) > 0) g_timeoutNs = atoll(getenv("X265HIP_CUSERVE_TIMEOUT_MS")) * 1000000ll;
         if (getenv("X265HIP_CUSERVE_SLOTS")) g_slots = atoi(getenv("X265HIP_CUSERVE_SLOTS"));
@@ -501,6 +513,7 @@ __attribute__((tls_model("initial-exec"))) thread_local const ScalingList* t_lis
 __attribute__((tls_model("initial-exec"))) thread_local uint64_t t_listEpoch = 0;
 __attribute__((tls_model("initial-exec"))) thread_local uint32_t t_listId = 0;
 __attribute__((tls_model("initial-exec"))) thread_local bool t_listKept = false;      // the last make_header refused its CU because of the list
+__attribute__((tls_model("initial-exec"))) thread_local bool t_lpKept = false;        // ... because the process's transforms are the low-pass ones and their jobs are not to be had
 __attribute__((tls_model("initial-exec"))) thread_local bool t_nrKept = false;        // ... because its denoise tables are not the frame encoder's own
 
 uint32_t scaling_lookup(const ScalingList* sl)
@@ -567,6 +580,38 @@ inline uint32_t scaling_id(const ScalingList* sl)
     return id;
 }
 
+// --lowpass-dct: `primitives` is filled once per process (primitives.cpp:250), so the low-pass transforms are a property of the process — of the first encoder
+// opened — not of an encoder's x265_param: what the table holds decides.  0: the standard transforms; 1: both sizes are the low-pass ones; -1: neither (a table
+// somebody else has written to: its CUs stay on the host)
+inline int table_lowpass()
+{
+    const bool l16 = primitives.cu[BLOCK_16x16].lowpass_dct && primitives.cu[BLOCK_16x16].dct == primitives.cu[BLOCK_16x16].lowpass_dct;
+    const bool l32 = primitives.cu[BLOCK_32x32].lowpass_dct && primitives.cu[BLOCK_32x32].dct == primitives.cu[BLOCK_32x32].lowpass_dct;
+    return l16 != l32 ? -1 : l16 ? 1 : 0;
+}
+
+// every service's kernels are the ones that hold the low-pass transforms (x265hip_cujob_lowpass, once per process); false: such CUs stay on the host
+bool lowpass_services()
+{
+    static std::atomic<int> state(0);
+    int st = state.load(std::memory_order_acquire);
+    if (!st)
+    {
+        static std::mutex once;
+        std::lock_guard<std::mutex> g(once);
+        if (!(st = state.load()))
+        {
+            // only a library that has the forms is asked (an older one, or the emulated one of the tests, has neither symbol)
+            st = g_lowpass && x265hip_cujob_features && x265hip_cujob_lowpass && (x265hip_cujob_features() & 8) && service() ? 1 : -1;
+            for (int k = 0; st > 0 && k < g_nsvc.load(std::memory_order_acquire); k++)
+                if (x265hip_cujob_lowpass(g_svc[k].cs))
+                    st = -1;
+            state.store(st, std::memory_order_release);
+        }
+    }
+    return st > 0;
+}
+
 } // namespace cusvc
 
 using namespace cusvc;
@@ -581,9 +626,18 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
     const bool codeChroma = csp != X265_CSP_I400 && se->m_frame->m_fencPic->m_picCsp != X265_CSP_I400;
     // RDOQ (presets slow / slower): the quantiser is Quant::rdoQuant and stays on the host (its decisions read the entropy coder's state); the job carries
     // the transforms in front of it — coefficient mode (X265HIP_CUSERVE_RDOQ=0 switches it off)
-    t_listKept = t_nrKept = false;
+    t_listKept = t_nrKept = t_lpKept = false;
     if (cu.m_tqBypass[0] || (q.m_rdoqLevel && !g_rdoqJobs) || csp < X265_CSP_I400 || csp > X265_CSP_I444 || (csp != X265_CSP_I400) != codeChroma)
         return false;
+    // --lowpass-dct (primitives.cpp:278-281; lowpassdct.cpp): the job carries X265HIP_CUJOB_LOWPASS and the device transforms its 16x16 and 32x32 units as the
+    // table's cu[].dct does — for a library that has the forms and services that were switched over to them; otherwise, and with X265HIP_CUSERVE_LOWPASS=0 (the default of the 8-bit
+    // and Main12 builds), these CUs stay on the host.  (The inverse jobs behind Quant::rdoQuant have nothing low-pass about them and go on as they are.)
+    const int lowpass = table_lowpass();
+    if (lowpass && (lowpass < 0 || !lowpass_services()))
+    {
+        t_lpKept = true;
+        return false;
+    }
     // noise reduction (quant.cpp:444-451): the job carries the offsets and the flag — for a library that has the denoise step (an older one, or the emulated one
     // of the tests, does not: these CUs then stay on the host, as they do unless X265HIP_CUSERVE_DENOISE=1), and for the frame encoder's own tables only.  Under
     // VBV emergency (frameencoder.cpp:576-583) `offset` points at the encoder-wide emergency tables and `residualSum` at one array all threads add to: the
@@ -625,7 +679,7 @@ bool make_header(Search* se, const Mode& mode, uint32_t log2CUSize, const uint32
         hdr.quantScale[p] = q.m_scalingList->m_quantCoef[3][3 + p][qp.rem][0];          // flat: every entry of every size and list is s_quantScales[rem]
         hdr.dequantScale[p] = ScalingList::s_invQuantScales[qp.rem];
     }
-    hdr.coefMode = (q.m_rdoqLevel ? 1u : 0u) | (denoise ? X265HIP_CUJOB_DENOISE : 0u);
+    hdr.coefMode = (q.m_rdoqLevel ? 1u : 0u) | (denoise ? X265HIP_CUJOB_DENOISE : 0u) | (lowpass ? X265HIP_CUJOB_LOWPASS : 0u);
     hdr.sourceDct = q.m_rdoqLevel && q.m_psyRdoqScale ? 1 : 0;
     return true;
 }
@@ -803,6 +857,7 @@ bool submit(Search* se, Mode& mode, uint32_t log2CUSize, ShortYuv& resiYuv, cons
     if (hdr.chroma > 1) counters().formatJobs.fetch_add(1, std::memory_order_relaxed);
     if (hdr.scaling) counters().scalingJobs.fetch_add(1, std::memory_order_relaxed);
     if (j.nr) counters().denoiseJobs.fetch_add(1, std::memory_order_relaxed);
+    if (hdr.coefMode & X265HIP_CUJOB_LOWPASS) counters().lowpassJobs.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -1231,6 +1286,17 @@ void report_scanhit()
 void x265hip_install_cuserve_slots(EncoderPrimitives& p)
 {
     decide();
+    {
+        // --lowpass-dct: setupCPrimitives has pointed the low-pass transforms' file statics (lowpassdct.cpp:117-121) at the standard_dct slots of the table it was
+        // given LAST — the bindings' private C table (x265hip_c_table, built by now or here), whose slots nobody fills (primitives.cpp:75-81 fills the process
+        // table's): lowPassDct16_c / lowPassDct32_c would call through null pointers.  Whichever build made the table (the product's x265_hip_primitives.cpp, the
+        // emulated one's), its slots are filled here, before enableLowpassDCTPrimitives can put the transforms into use.  (The table is a static object of its TU.)
+        static std::mutex onceL;
+        std::lock_guard<std::mutex> g(onceL);
+        EncoderPrimitives& c = const_cast<EncoderPrimitives&>(x265hip_c_table());
+        for (int k = 0; k < NUM_TR_SIZE; k++)
+            if (!c.cu[k].standard_dct) c.cu[k].standard_dct = c.cu[k].dct;
+    }
     if (getenv("X265HIP_DEBUG_SCANHIT"))
     {
         static std::mutex onceS;
@@ -1451,6 +1517,7 @@ void Search::encodeResAndCalcRdInterCU(Mode& interMode, const CUGeom& cuGeom)
             counters().skipped.fetch_add(1, std::memory_order_relaxed);
             if (t_listKept) counters().scalingKept.fetch_add(1, std::memory_order_relaxed);
             if (t_nrKept) counters().denoiseKept.fetch_add(1, std::memory_order_relaxed);
+            if (t_lpKept) counters().lowpassKept.fetch_add(1, std::memory_order_relaxed);
         }
         else
             t_job.inTree = false;

@@ -41,6 +41,8 @@ extern "C" uint32_t x265hip_cujob_features(void) __attribute__((weak));
 extern "C" int x265hip_cujob_scaling_add(x265hip_cuserve* cs, const int32_t* quantCoef, const int32_t* dequantCoef, uint32_t* id) __attribute__((weak));
 // likewise: absent (or bit 1 of the features clear) = no denoise jobs, CUs of an encode with noise reduction stay on the host
 extern "C" int x265hip_cujob_denoise(x265hip_cuserve* cs, int slot, uint16_t** offsets, const uint16_t** absCoef) __attribute__((weak));
+// likewise: absent (or bit 3 of the features clear) = no low-pass jobs, CUs of a --lowpass-dct process stay on the host
+extern "C" int x265hip_cujob_lowpass(x265hip_cuserve* cs) __attribute__((weak));
 
 namespace X265_NS {
 

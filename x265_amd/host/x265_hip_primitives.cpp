@@ -44,6 +44,9 @@ static void ensure_c_table()
         memset(&g_c, 0, sizeof(g_c));
         setupCPrimitives(g_c);
         setupAliasPrimitives(g_c);
+        // setupCPrimitives has pointed the low-pass transforms' file statics (lowpassdct.cpp:117-121) at THIS table's standard_dct slots, which nobody else
+        // fills (primitives.cpp:75-81 fills the process table's): a --lowpass-dct encode would call through null pointers
+        for (int k = 0; k < NUM_TR_SIZE; k++) g_c.cu[k].standard_dct = g_c.cu[k].dct;
         g_cReady = true;
     }
 }
