@@ -1,4 +1,4 @@
-// refpic.h — the reference-picture mirror's state and its worker thread, shared by refpic.hip (sub-pel planes) and sadsurf.hip (SAD surfaces
+// refpic.h — the reference-picture mirror's state and its worker thread, shared by refpic.hip (sub-pel planes) and surfbuild.hip (SAD surfaces
 // that follow a mirror's progress).  Not part of the C ABI.
 #pragma once
 #include "common.h"
@@ -43,12 +43,12 @@ struct x265hip_refpic
     std::atomic<uint32_t> epoch{ 0 };         // bumped by reset(): queued work of an older picture is dropped
     std::atomic<int> pending{ 0 };            // queued + running jobs
     std::atomic<int> failed{ 0 };
-    std::vector<x265hip_sadsurf*> surfaces;   // SAD surfaces attached to this picture (worker only; sadsurf.hip)
+    std::vector<x265hip_sadsurf*> surfaces;   // SAD surfaces attached to this picture (worker only; surfbuild.hip)
 };
 
 namespace xh {
 
-// kind 0: rows [0, rowsFinal) of rp's picture are final.  kind 1 / 2: attach / release the SAD surface `ss` (sadsurf.hip); rp may be null for a
+// kind 0: rows [0, rowsFinal) of rp's picture are final.  kind 1 / 2: attach / release the SAD surface `ss` (surfbuild.hip); rp may be null for a
 // release whose picture has gone
 struct RefJob { x265hip_refpic* rp; int rowsFinal; uint32_t epoch; int kind = 0; x265hip_sadsurf* ss = nullptr; };
 
@@ -107,7 +107,7 @@ struct RefWorker
 };
 
 
-// sadsurf.hip, called on the worker thread
+// surfbuild.hip, called on the worker thread
 void sadsurf_rows_arrived(x265hip_refpic* rp);            // after a band of rp has been uploaded (and its planes published)
 void sadsurf_job(const RefJob& j);                        // kinds 1 and 2
 void sadsurf_attach_batch(const std::vector<RefJob>& jobs);   // kind 1 jobs that were queued together

@@ -91,7 +91,7 @@ void RefWorker::run()
         if (j.kind == 1)
         {
             // a surface being attached: the first search of a frame against each of its reference pictures attaches one, microseconds apart — give the
-            // siblings X265HIP_SADSURF_GATHER_US (default 100) to arrive and build them all in one launch (sadsurf.hip progress_multi); the attach jobs at the front of the queue only,
+            // siblings X265HIP_SADSURF_GATHER_US (default 100) to arrive and build them all in one launch (surfbuild.hip progress_multi); the attach jobs at the front of the queue only,
             // so that nothing overtakes a band
             static const int gatherUs = getenv("X265HIP_SADSURF_GATHER_US") ? atoi(getenv("X265HIP_SADSURF_GATHER_US")) : 100;
             std::vector<RefJob> batch(1, j);

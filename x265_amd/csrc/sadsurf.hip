@@ -3,8 +3,9 @@
 // MotionEstimate::motionEstimate (reference source/encoder/motion.cpp:739-1569) measures an integer-pel candidate as
 // sad(fenc, FENC_STRIDE, fref + mx + my * stride, stride) (:246-330) — a function of the source picture, the finished reference picture, the
 // block's position and the vector, and of nothing the encoder decides.  One surface = one (source picture, reference picture) pair: for every
-// aligned 16 / 32 / 64 block a 16 x 16 window of vectors, built here as the reference picture's rows arrive (the refpic worker calls
-// sadsurf_rows_arrived after each band) and mirrored into page-locked host memory, where x265_amd/host/x265_hip_sadplanes.cpp reads them.
+// aligned 16 / 32 / 64 block a 16 x 16 window of vectors, built by the kernels here as the reference picture's rows arrive and mirrored into page-locked
+// host memory, where x265_amd/host/x265_hip_sadplanes.cpp reads them.  This file is the kernels and nothing else: the host side (surfbuild.hip) reaches
+// them through the launch interface at the end (sadsurf.h), and the counter profiles stamped `# sources sadsurf.hip` cover exactly this text.
 //
 // The kernel is the search-window kernel of the design: one workgroup per 64 x 64 region (CTU), 16 waves.
 //   stage    the source CTU (4 KB) and the reference window (64 + 2S)^2 around it (16 KB at S = 32) go to LDS once;
@@ -20,65 +21,14 @@
 // CPU by the test tier).  16-bit pictures (Main10 / Main12 builds) have a kernel of their own below: v_sad_u16, u32 surfaces — in LDS up to a range of 16, in
 // device memory above it.
 #include "common.h"
-#include "internal.h"
-#include "refpic.h"
+#include "sadsurf.h"
+#include "surfplan.h"
 #include "tiles.h"
-#include <cstring>
+#include <atomic>
+#include <cstdlib>
 #include <type_traits>
-#include <map>
-#include <utility>
-
-struct x265hip_srcpic
-{
-    int depth = 8, w = 0, h = 0, device = 0;
-    int place = -1;                     // x265hip_srcpic_create_at; -(device + 1) for x265hip_srcpic_create
-    int64_t pitch = 0;                  // bytes between rows of dLuma
-    char* dLuma = nullptr;
-    char* hStage = nullptr;             // page-locked staging copy (the encoder's buffer is ordinary memory)
-    // (no stream: x265hip_srcpic_upload leases one from the pool, runtime.hip stream_lease)
-    std::atomic<int> refs{ 1 };         // the creator's + one per SAD surface attached: a surface reads dLuma and files its buffers under `device` until it is freed,
-                                        // so x265hip_srcpic_destroy only drops the creator's reference (a resized source buffer used to free under them)
-};
-static void srcpic_unref(x265hip_srcpic* sp);
 
 namespace xh {
-
-constexpr int kWin = X265HIP_SADSURF_WIN;
-
-struct SurfLayout
-{
-    int blocksX[4], blocksY[4], per[4], entryBytes[4];
-    int64_t originOff[4], tableOff[4];   // byte offsets inside a CTU row's chunk
-    int64_t subpelOff[4];                 // sub-pel SATD tables (levels 1..3 when bit 4 of `levels` is set; 0 = not built)
-    int64_t pitch;                        // bytes per CTU row
-    int ctuCols, ctuRows;
-};
-
-// one surface's share of a launch: rows [row0, row0 + rows) of its table
-struct SurfJob
-{
-    const uint8_t* ref; int64_t refStride;       // the job's reference pixel (0, 0): the surfaces of one launch may follow different reference pictures
-    const uint8_t* src; int64_t srcPitch;
-    char* out;                                    // device table buffer (chunk of CTU row 0 first)
-    int S, lambda20, row0, rows;
-    int level0;                                   // the 8x8 windows are wanted
-};
-constexpr int kMaxJobs = 16;
-
-// one launch: rows of up to kMaxJobs surfaces that share the geometry and the table layout (same encoder, same levels) — of one reference picture or several
-struct SurfArgs
-{
-    int picW, picH, marginX, marginY;
-    int bufRows;                                  // rows of the padded picture in device memory (marginY above picture row 0)
-    int64_t pitch;
-    int64_t originOff[4], tableOff[4];
-    int blocksX[4];
-    int blocksY0;                                 // 8x8 blocks inside the picture, vertically
-    int nJobs;
-    int xcd;                                      // 1: XCD-aware CTU order (surf_ctu below)
-    int64_t subpelOff3;                           // >= 0: the CTU's 49 sub-pel SATD entries of the 64x64 level are zeroed (subpel_satd_kernel_lds adds four quadrants into them)
-    SurfJob job[kMaxJobs];
-};
 
 // Which CTU of the launch a workgroup takes.  Workgroups are dealt to the eight XCDs round-robin in dispatch order (x fastest), and the windows of neighbouring
 // CTUs overlap by half either way: in the plain order a row's neighbours sit in eight different L2s and each fetches the shared half again.  XCD x instead walks a
@@ -92,59 +42,6 @@ __device__ __forceinline__ void surf_ctu(int xcd, int& cx, int& rowIn)
     const int x = L & 7, i = L >> 3, per = total >> 3, rem = total & 7;
     const int c = x * per + (x < rem ? x : rem) + i;
     cx = c % (int)gridDim.x; rowIn = c / (int)gridDim.x;
-}
-
-} // namespace xh
-
-struct x265hip_sadsurf
-{
-    x265hip_srcpic* src = nullptr;
-    x265hip_refpic* ref = nullptr;       // null once the reference picture has gone (under g_ssLock)
-    int workerPlace = -1;                // the worker that drives this surface (its reference picture's place)
-    xh::Replica* rep = nullptr;          // the reference picture's replica at the source's place; null: the mirror itself (same place).  Worker only
-    int S = 32, lambda20 = 0, levels = 14;
-    xh::SurfLayout lay;
-    char* dBuf = nullptr;                // ctuRows * pitch
-    char* hBuf = nullptr;                // page-locked mirror, same layout
-    size_t bytes = 0;
-    int rowsBuilt = 0;                   // worker only
-    std::atomic<int> ctuRowsReady{ 0 };
-    x265hip_sadsurf_view view;
-    std::atomic<bool> released{ false };
-};
-
-namespace xh {
-
-static std::mutex g_ssLock;              // the surfaces lists of the mirrors and x265hip_sadsurf::ref
-static std::mutex g_poolLock;
-struct PoolEntry { char* d; char* h; };
-static std::multimap<std::pair<size_t, int>, PoolEntry> g_pool;      // key: (bytes, device of d)      // table buffers of finished surfaces, by size (pinned allocations are expensive: ~ms)
-static std::atomic<uint64_t> g_statAttached{ 0 }, g_statRows{ 0 }, g_statLaunches{ 0 };
-static std::atomic<uint64_t> g_statReplicas{ 0 }, g_statPeerBands{ 0 }, g_statPeerBytes{ 0 };
-
-static void layout_for(int w, int h, int depth, int levels, SurfLayout& L)
-{
-    memset(&L, 0, sizeof(L));
-    L.ctuCols = (w + 63) / 64; L.ctuRows = (h + 63) / 64;
-    int64_t off = 0;
-    for (int l = 0; l < 4; l++)
-    {
-        if (!(levels >> l & 1))
-            continue;                             // level not built: no room in the chunks, blocksX = 0
-        const int N = 8 << l;
-        L.blocksX[l] = w / N; L.blocksY[l] = h / N; L.per[l] = 64 / N;
-        L.entryBytes[l] = (uint64_t)N * N * ((1u << depth) - 1) < 65536 ? 2 : 4;
-        L.originOff[l] = off; off += (int64_t)L.per[l] * L.blocksX[l] * 4;
-        off = (off + 15) & ~(int64_t)15;
-        L.tableOff[l] = off; off += (int64_t)L.per[l] * L.blocksX[l] * kWin * kWin * L.entryBytes[l];
-        off = (off + 15) & ~(int64_t)15;
-        if (l && (levels & 16))
-        {
-            L.subpelOff[l] = off; off += (int64_t)L.per[l] * L.blocksX[l] * X265HIP_SADSURF_SUBPEL * 4;
-            off = (off + 15) & ~(int64_t)15;
-        }
-    }
-    L.pitch = (off + 255) & ~(int64_t)255;
 }
 
 // ---- the kernel ---------------------------------------------------------------------------------------------------------------------------
@@ -712,17 +609,6 @@ __global__ __launch_bounds__(1024) void sadsurf_ctu16_wide_kernel(SurfArgs a, ui
 // 4 fy + fx — for the 7 x 7 vectors q = 4 c + (dx, dy) around the window's centre c = origin + WIN / 2 of every block of levels 1..3.  A job = one
 // (block, vector); a wave runs 64 / T jobs at once, T = lanes per job (one 4x4 tile each per step), as pixcmp_kernel<SATD> does (pixel.hip); the SATD of
 // a 16x16 / 32x32 / 64x64 block is the sum over its 4x4 tiles of (sum |H d H^T|) >> 1 (pixel.cpp:210-297: satd8<w, h> over satd_8x4).
-struct SubpelArgs
-{
-    const void* pic; const void* planes; int64_t stride, planeElems;        // reference: pixel (0, 0) of the picture / of plane 0; planes 1..15 follow
-    const void* src; int64_t srcPitch;                                      // source luma, bytes per row
-    char* out;                                                              // the surface's device chunks
-    int64_t pitch, originOff[4], subpelOff[4];
-    int blocksX[4], blocksY[4], per[4];
-    int row0, rows;
-    int jobs[4];                                                            // (block, vector) jobs of levels 1..3 in this launch: prefix sums
-    int xcd;                                                                // 1: XCD-aware job order (the grid is a multiple of 128)
-};
 template <typename P>
 __global__ __launch_bounds__(256) void subpel_satd_kernel(SubpelArgs a)
 {
@@ -1018,6 +904,15 @@ __global__ __launch_bounds__(256) void subpel_satd_kernel_lds(SubpelArgs a)
     }
 }
 
+
+// ---- the launch interface (sadsurf.h): the only way the builder reaches the kernels above ----------------------------------------------------
+
+static size_t surf_lds_bytes(int S)
+{
+    const int D = 2 * S, RW = 64 + D + 8;
+    return 4096 + (size_t)(64 + D) * RW + (size_t)16 * D * D * 2;
+}
+
 static size_t surf16_lds_bytes(int S)
 {
     const int D = 2 * S, RWD = (64 + D) / 2 + 4;
@@ -1030,688 +925,54 @@ static size_t surf16_wide_lds_bytes(int S)
     const int D = 2 * S, RWD = (64 + D) / 2 + 4;
     return (size_t)64 * 32 * 4 + (size_t)2 * (64 + D) * RWD * 4;
 }
-static bool surf16_wide(int depth, int S) { return depth != 8 && S > 16; }
+bool surf16_wide(int depth, int S) { return depth != 8 && S > 16; }
 
-// The wide form's surfaces: one buffer per launch in flight, `groups` regions of 16 x (2 maxS)^2 u32 (256 KB at S = 32).  A launch takes a buffer of its device
-// that no other launch holds — the workers of two places on one device, or a replica's stream next to its mirror's, may launch at the same time — and gives it
-// back once its stream is synchronised; buffers are kept for the next launch and only ever replaced by larger ones (device allocations cost milliseconds).
-struct WideBuf { int dev; size_t bytes; char* d; bool busy; };
-static std::vector<WideBuf> g_wide;                     // under g_poolLock
-static char* wide_take(int dev, size_t bytes)
+// the dynamic LDS limit is a per-device attribute of the kernel
+bool raise_lds_limits(int dev)
 {
-    char* old = nullptr;
+    static std::atomic<uint64_t> attrSet{ 0 };
+    if (!(attrSet.load() >> dev & 1))
     {
-        std::lock_guard<std::mutex> g(g_poolLock);
-        size_t small = g_wide.size();
-        for (size_t i = 0; i < g_wide.size(); i++)
-        {
-            WideBuf& b = g_wide[i];
-            if (b.busy || b.dev != dev) continue;
-            if (b.bytes >= bytes) { b.busy = true; return b.d; }
-            small = i;
-        }
-        if (small < g_wide.size()) { old = g_wide[small].d; g_wide[small] = g_wide.back(); g_wide.pop_back(); }
+        if (hipFuncSetAttribute((const void*)sadsurf_ctu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf_lds_bytes(32)) != hipSuccess ||
+            hipFuncSetAttribute((const void*)sadsurf_ctu16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_lds_bytes(16)) != hipSuccess ||
+            hipFuncSetAttribute((const void*)sadsurf_ctu16_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_wide_lds_bytes(32)) != hipSuccess)
+            return false;
+        attrSet |= (uint64_t)1 << dev;
     }
-    if (old) (void)device_free(old);                    // too small and idle: replaced (the caller has made `dev` current)
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    std::lock_guard<std::mutex> g(g_poolLock);
-    g_wide.push_back(WideBuf{ dev, bytes, d, true });
-    return d;
-}
-static void wide_return(char* d)
-{
-    if (!d) return;
-    std::lock_guard<std::mutex> g(g_poolLock);
-    for (WideBuf& b : g_wide)
-        if (b.d == d) b.busy = false;
+    return true;
 }
 
-static size_t surf_lds_bytes(int S)
+bool launch_windows(const SurfArgs& a, int depth, int maxS, int cols, int rows, hipStream_t st, char* wideBuf, int wideGroups)
 {
-    const int D = 2 * S, RW = 64 + D + 8;
-    return 4096 + (size_t)(64 + D) * RW + (size_t)16 * D * D * 2;
+    if (depth == 8)
+        hipLaunchKernelGGL(sadsurf_ctu_kernel, dim3(cols, rows), dim3(1024), surf_lds_bytes(maxS), st, a);
+    else if (surf16_wide(depth, maxS))
+        hipLaunchKernelGGL(sadsurf_ctu16_wide_kernel, dim3(wideGroups), dim3(1024), surf16_wide_lds_bytes(maxS), st, a, (uint32_t*)wideBuf, (int64_t)16 * (2 * maxS) * (2 * maxS), cols,
+                           cols * rows);
+    else
+        hipLaunchKernelGGL(sadsurf_ctu16_kernel, dim3(cols, rows), dim3(1024), surf16_lds_bytes(maxS), st, a);
+    return hipGetLastError() == hipSuccess;
 }
 
-// rows of `ss` that the reference's uploaded rows allow now: [ss->rowsBuilt, returned value)
-static int rows_possible(x265hip_sadsurf* ss)
+bool launch_subpel(const SubpelArgs& sa, int depth, int B, bool quadrantSums, hipStream_t st)
 {
-    x265hip_refpic* rp = ss->ref;
-    if (!rp || rp->failed.load() || ss->released)
-        return ss->rowsBuilt;
-    const bool complete = rp->uploaded >= rp->marginY + rp->picH + rp->marginY;
-    const int finalPic = rp->uploaded - rp->marginY;           // picture rows [.., finalPic) are on the device
-    int r1 = ss->rowsBuilt;
-    while (r1 < ss->lay.ctuRows && (complete || 64 * (r1 + 1) + ss->S <= finalPic))
-        r1++;
-    return r1;
-}
-
-// the replica of rp at `place`, created on first use (worker thread)
-static Replica* replica_at(x265hip_refpic* rp, int place)
-{
-    for (Replica* r : rp->replicas)
-        if (r->place == place) return r;
-    const int dev = place_device(place);
-    if (dev < 0 || hipSetDevice(dev) != hipSuccess)
-        return nullptr;
-    Replica* r = new Replica;
-    r->place = place; r->device = dev;
-    const size_t bytes = (size_t)rp->planeElems * rp->B;
-    // (the planes: 16 x the picture, plane 0 unused, as in the mirror itself; without them the replica serves integer-pel surfaces only)
-    if (hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&r->dPic, bytes) != hipSuccess)
+    static const bool ldsForm = !(getenv("X265HIP_SUBPEL_LDS") && !atoi(getenv("X265HIP_SUBPEL_LDS")));
+    // the second form adds the quadrants of a 64x64 block into its entries: only behind a window kernel that has zeroed them (subpel_quadrant_sums); it
+    // stages whole dwords, so the reference's rows and planes must start on one
+    if (quadrantSums && (depth == 8 || depth == 10) && ldsForm && sa.stride * B % 4 == 0 && sa.planeElems * B % 4 == 0)
     {
-        if (r->st) (void)hipStreamDestroy(r->st);
-        delete r;
-        (void)hipSetDevice(rp->device);
-        return nullptr;
+        const int blocks1 = sa.jobs[1] / X265HIP_SADSURF_SUBPEL, blocks2 = (sa.jobs[2] - sa.jobs[1]) / X265HIP_SADSURF_SUBPEL, blocks3 = (sa.jobs[3] - sa.jobs[2]) / X265HIP_SADSURF_SUBPEL;
+        const int grid = plan::subpel_lds_grid(plan::subpel_lds_groups(blocks1, blocks2, blocks3));
+        if (depth == 8)
+            hipLaunchKernelGGL(subpel_satd_kernel_lds<uint8_t>, dim3(grid), dim3(256), 0, st, sa);
+        else
+            hipLaunchKernelGGL(subpel_satd_kernel_lds<uint16_t>, dim3(grid), dim3(256), 0, st, sa);
     }
-    if (dev != rp->device)
-    {
-        // direct access between the two GPUs where the fabric offers it (xGMI inside a node); hipMemcpyPeerAsync works either way
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, dev, rp->device) == hipSuccess && can && hipDeviceEnablePeerAccess(rp->device, 0) != hipSuccess)
-            (void)hipGetLastError();                       // already enabled
-    }
-    if (hipMalloc((void**)&r->dPlanes, 16 * bytes) != hipSuccess) { (void)hipGetLastError(); r->dPlanes = nullptr; }
-    (void)hipSetDevice(rp->device);
-    rp->replicas.push_back(r);
-    g_statReplicas++;
-    return r;
-}
-
-// Build what the references' rows allow of every surface attached to the pictures in `rps` (worker thread; the bands' uploads have been synchronised).
-// Surfaces that share geometry, table layout and the device they are built on go into ONE launch, whichever reference picture they follow (a job
-// carries its own reference pointer): the three surfaces a P frame attaches within microseconds of each other — one per reference picture — are
-// 1530 CTUs together, 7 rounds of the 224 CUs the job server leaves free at 0.98 fill, where three launches of 510 CTUs are 3 rounds each at 0.76.
-// Surfaces whose source lives at another place are built from the replica there, after the rows it lacks have been pushed device to device.
-//
-// 148 KB of LDS = one workgroup per CU: a launch takes ceil(CTUs / free CUs) rounds of the same ~54 us whatever the last round holds.  While a
-// reference picture is still arriving, its newest rows — the ones no search is waiting for yet — are left out when they would only open a round that
-// stays less than 3/4 full; they go with the next band, or with the picture's last band, which takes everything.  X265HIP_SADSURF_ROUNDS=0: every launch
-// takes all it can.
-struct SurfItem { x265hip_sadsurf* ss; x265hip_refpic* rp; Replica* rep; int dev; int take; bool arriving; };
-
-static void fail_refs(const std::vector<SurfItem>& items, size_t from, size_t to)
-{
-    for (size_t k = from; k < to; k++) items[k].rp->failed = 1;
-}
-
-static void progress_multi(const std::vector<x265hip_refpic*>& rps)
-{
-    static const bool rounds = !(getenv("X265HIP_SADSURF_ROUNDS") && !atoi(getenv("X265HIP_SADSURF_ROUNDS")));
-    std::vector<SurfItem> items;
-    for (x265hip_refpic* rp : rps)
-    {
-        if (rp->failed.load()) continue;
-        std::vector<x265hip_sadsurf*> list;
-        {
-            std::lock_guard<std::mutex> g(g_ssLock);
-            list = rp->surfaces;
-        }
-        const bool arriving = rp->uploaded < rp->marginY + rp->picH + rp->marginY;
-        for (x265hip_sadsurf* ss : list)
-        {
-            if (ss->ref != rp) continue;
-            const int take = rows_possible(ss) - ss->rowsBuilt;
-            if (take > 0)
-                items.push_back(SurfItem{ ss, rp, ss->rep, ss->rep ? ss->rep->device : rp->device, take, arriving });
-        }
-    }
-    if (items.empty())
-        return;
-    // same device, geometry and table layout next to each other (stable: the order of `rps` and of the surfaces inside a group is kept)
-    auto same_group = [](const SurfItem& x, const SurfItem& y) {
-        return x.dev == y.dev && x.ss->levels == y.ss->levels && x.rp->depth == y.rp->depth && x.rp->picW == y.rp->picW && x.rp->picH == y.rp->picH &&
-               surf16_wide(x.rp->depth, x.ss->S) == surf16_wide(y.rp->depth, y.ss->S) &&           // (a launch is of one kernel form)
-               x.rp->marginX == y.rp->marginX && x.rp->marginY == y.rp->marginY && x.rp->bufRows == y.rp->bufRows && x.ss->lay.pitch == y.ss->lay.pitch; };
-    {
-        std::vector<SurfItem> sorted;
-        std::vector<bool> used(items.size(), false);
-        for (size_t a0 = 0; a0 < items.size(); a0++)
-        {
-            if (used[a0]) continue;
-            for (size_t b0 = a0; b0 < items.size(); b0++)
-                if (!used[b0] && same_group(items[a0], items[b0])) { used[b0] = true; sorted.push_back(items[b0]); }
-        }
-        items.swap(sorted);
-    }
-    size_t g0 = 0;
-    while (g0 < items.size())
-    {
-        size_t g1 = g0 + 1;
-        while (g1 < items.size() && same_group(items[g0], items[g1])) g1++;
-        // whole rounds: rows of pictures that are still arriving may stay behind
-        if (rounds)
-        {
-            const int cols = items[g0].ss->lay.ctuCols, cus = free_compute_units(items[g0].dev);
-            int rows = 0, spare = 0;
-            for (size_t k = g0; k < g1; k++) { rows += items[k].take; if (items[k].arriving) spare += items[k].take; }
-            if (cols > 0 && cols <= cus && rows * cols > cus)
-            {
-                const int rowsPerRound = cus / cols;
-                int excess = rows % rowsPerRound;
-                if (excess * 4 < rowsPerRound * 3 && excess <= spare)
-                    for (size_t k = g1; k-- > g0 && excess > 0;)
-                        if (items[k].arriving)
-                        {
-                            const int d = items[k].take < excess ? items[k].take : excess;
-                            items[k].take -= d; excess -= d;
-                        }
-            }
-        }
-        size_t i = g0;
-        while (i < g1)
-        {
-            SurfArgs a;
-            memset(&a, 0, sizeof(a));
-            static const bool xcdOrderCtu = !(getenv("X265HIP_SADSURF_XCD") && !atoi(getenv("X265HIP_SADSURF_XCD")));
-            a.xcd = xcdOrderCtu ? 1 : 0;
-            size_t in[kMaxJobs];
-            int upto[kMaxJobs], rows = 0, maxS = 0;
-            for (; i < g1 && a.nJobs < kMaxJobs; i++)
-            {
-                const SurfItem& it = items[i];
-                if (it.take <= 0)
-                    continue;
-                x265hip_sadsurf* ss = it.ss;
-                const char* dPic = it.rep ? it.rep->dPic : it.rp->dPic;
-                SurfJob& j = a.job[a.nJobs];
-                j.ref = (const uint8_t*)dPic + ((size_t)it.rp->marginY * it.rp->stride + it.rp->marginX) * it.rp->B; j.refStride = it.rp->stride;   // stride in samples
-                j.src = (const uint8_t*)ss->src->dLuma; j.srcPitch = ss->src->pitch;
-                j.out = ss->dBuf; j.S = ss->S; j.lambda20 = ss->lambda20; j.row0 = ss->rowsBuilt; j.rows = it.take;
-                j.level0 = (ss->levels & 1) && it.rp->depth == 8;
-                in[a.nJobs] = i; upto[a.nJobs] = ss->rowsBuilt + it.take;
-                rows += j.rows;
-                if (ss->S > maxS) maxS = ss->S;
-                a.nJobs++;
-            }
-            if (!a.nJobs)
-                break;
-            const SurfItem& first = items[in[0]];
-            x265hip_refpic* rp0 = first.rp;
-            const int dev = first.dev;
-            hipStream_t st = first.rep ? first.rep->st : rp0->st;
-            if (hipSetDevice(dev) != hipSuccess) { fail_refs(items, g0, g1); return; }
-            // the reconstructed rows a replica lacks, straight from the owner's device memory (on the replica's stream, waited for: the launch below may
-            // run on another reference's stream)
-            for (int k = 0; k < a.nJobs; k++)
-            {
-                const SurfItem& it = items[in[k]];
-                if (!it.rep || it.rep->copied >= it.rp->uploaded)
-                    continue;
-                const size_t off = (size_t)it.rep->copied * it.rp->stride * it.rp->B, bytes = (size_t)(it.rp->uploaded - it.rep->copied) * it.rp->stride * it.rp->B;
-                if (hipMemcpyPeerAsync(it.rep->dPic + off, it.rep->device, it.rp->dPic + off, it.rp->device, bytes, it.rep->st) != hipSuccess ||
-                    hipStreamSynchronize(it.rep->st) != hipSuccess)
-                {
-                    set_error(X265HIP_EHIP, "sadsurf: device-to-device push of reference rows failed");
-                    fail_refs(items, g0, g1);
-                    (void)hipSetDevice(rp0->device);
-                    return;
-                }
-                g_statPeerBands++;
-                g_statPeerBytes += bytes;
-                it.rep->copied = it.rp->uploaded;
-                // the replica's own sub-pel planes of the rows whose support (y - 3 .. y + 4) has arrived — the same filter launch as the mirror's band
-                // (refpic.hip process()), on the replica's device and stream; waited for below with the stream the surfaces are built on
-                const int phaseEnd = it.rep->copied - 4;
-                if (it.rep->dPlanes && phaseEnd > it.rep->phaseDone)
-                {
-                    x265hip_refpic* rp = it.rp;
-                    const char* org = it.rep->dPic + ((size_t)rp->marginY * rp->stride + rp->marginX) * rp->B;
-                    char* porg = it.rep->dPlanes + ((size_t)rp->marginY * rp->stride + rp->marginX) * rp->B;
-                    DevSpan spanP(X265HIP_CLK_PLANES, it.rep->st);
-                    if (build_subpel_rows(rp->depth, org, rp->stride, -rp->marginX + 4, rp->picW + rp->marginX - 4, it.rep->phaseDone - rp->marginY, phaseEnd - rp->marginY, porg,
-                                          rp->planeElems, it.rep->st) || hipStreamSynchronize(it.rep->st) != hipSuccess)
-                    {
-                        set_error(X265HIP_EHIP, "sadsurf: sub-pel planes of a replica failed");
-                        fail_refs(items, g0, g1);
-                        (void)hipSetDevice(rp0->device);
-                        return;
-                    }
-                    spanP.end();
-                    spanP.bytes = (uint64_t)(phaseEnd - it.rep->phaseDone) * (uint64_t)(rp->picW + 2 * rp->marginX - 8) * 16 * rp->B;
-                    spanP.commit();
-                    it.rep->phaseDone = phaseEnd;
-                }
-            }
-            const SurfLayout& lay = first.ss->lay;            // same picture size and levels: same layout
-            a.picW = rp0->picW; a.picH = rp0->picH; a.marginX = rp0->marginX; a.marginY = rp0->marginY; a.bufRows = rp0->bufRows;
-            a.pitch = lay.pitch;
-            for (int l = 0; l < 4; l++) { a.originOff[l] = lay.originOff[l]; a.tableOff[l] = lay.tableOff[l]; a.blocksX[l] = lay.blocksX[l]; }
-            a.blocksY0 = lay.blocksY[0];
-            // (8- and 10-bit pictures with sub-pel tables: the window kernel zeroes the 64x64 level's entries, which subpel_satd_kernel_lds then adds into)
-            a.subpelOff3 = (first.ss->levels & 16) && (rp0->depth == 8 || rp0->depth == 10) ? lay.subpelOff[3] : -1;
-            // the dynamic LDS limit is a per-device attribute of the kernel
-            static std::atomic<uint64_t> attrSet{ 0 };
-            if (!(attrSet.load() >> dev & 1))
-            {
-                if (hipFuncSetAttribute((const void*)sadsurf_ctu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf_lds_bytes(32)) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)sadsurf_ctu16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_lds_bytes(16)) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)sadsurf_ctu16_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)surf16_wide_lds_bytes(32)) != hipSuccess)
-                {
-                    set_error(X265HIP_EHIP, "sadsurf: cannot raise the dynamic LDS limit");
-                    fail_refs(items, g0, g1);
-                    (void)hipSetDevice(rp0->device);
-                    return;
-                }
-                attrSet |= (uint64_t)1 << dev;
-            }
-            // the launch between two events of its own stream: the kernel's device time (x265hip_device_time, x265hip_sadsurf_stats)
-            // the wide form: as many workgroups as the device holds at once (one per free CU: 16 waves of 128 registers), each with a region of the pooled buffer;
-            // X265HIP_SADSURF_WIDE_GROUPS bounds the grid further (read per launch: the tests walk several CTUs per workgroup on small pictures with it)
-            const bool wide = surf16_wide(rp0->depth, maxS);
-            char* wideBuf = nullptr;
-            int wideGroups = 0;
-            const int64_t regionElems = (int64_t)16 * (2 * maxS) * (2 * maxS);
-            if (wide)
-            {
-                const int total = lay.ctuCols * rows, cap = getenv("X265HIP_SADSURF_WIDE_GROUPS") ? atoi(getenv("X265HIP_SADSURF_WIDE_GROUPS")) : 0;
-                wideGroups = free_compute_units(dev);
-                if (cap > 0 && cap < wideGroups) wideGroups = cap;
-                if (total < wideGroups) wideGroups = total;
-                if (!(wideBuf = wide_take(dev, (size_t)wideGroups * regionElems * 4)))
-                {
-                    set_error(X265HIP_ENOMEM, "sadsurf: %zu bytes for the surfaces of a launch at range %d", (size_t)wideGroups * regionElems * 4, maxS);
-                    fail_refs(items, g0, g1);
-                    (void)hipSetDevice(rp0->device);
-                    return;
-                }
-            }
-            DevSpan span(X265HIP_CLK_SADSURF, st);
-            if (rp0->depth == 8)
-                hipLaunchKernelGGL(sadsurf_ctu_kernel, dim3(lay.ctuCols, rows), dim3(1024), surf_lds_bytes(maxS), st, a);
-            else if (wide)
-                hipLaunchKernelGGL(sadsurf_ctu16_wide_kernel, dim3(wideGroups), dim3(1024), surf16_wide_lds_bytes(maxS), st, a, (uint32_t*)wideBuf, regionElems, lay.ctuCols,
-                                   lay.ctuCols * rows);
-            else
-                hipLaunchKernelGGL(sadsurf_ctu16_kernel, dim3(lay.ctuCols, rows), dim3(1024), surf16_lds_bytes(maxS), st, a);
-            bool bad = hipGetLastError() != hipSuccess;
-            span.end();
-            DevSpan span2(X265HIP_CLK_SUBPEL, st);
-            // the sub-pel SATD tables of the rows just built (same stream: the origins are there)
-            for (int k = 0; k < a.nJobs && !bad; k++)
-            {
-                const SurfItem& it = items[in[k]];
-                if (!(it.ss->levels & 16) || (it.rep && !it.rep->dPlanes))
-                    continue;
-                x265hip_refpic* rp = it.rp;
-                SubpelArgs sa;
-                memset(&sa, 0, sizeof(sa));
-                // (a surface at another place than its reference's mirror: the replica's rows and the replica's own planes)
-                sa.pic = (it.rep ? it.rep->dPic : rp->dPic) + ((size_t)rp->marginY * rp->stride + rp->marginX) * rp->B;
-                sa.planes = (it.rep ? it.rep->dPlanes : rp->dPlanes) + ((size_t)rp->marginY * rp->stride + rp->marginX) * rp->B;
-                sa.stride = rp->stride; sa.planeElems = rp->planeElems;
-                sa.src = a.job[k].src; sa.srcPitch = a.job[k].srcPitch;
-                sa.out = a.job[k].out; sa.pitch = lay.pitch;
-                sa.row0 = a.job[k].row0; sa.rows = a.job[k].rows;
-                for (int l = 1; l < 4; l++)
-                {
-                    sa.originOff[l] = lay.originOff[l]; sa.subpelOff[l] = lay.subpelOff[l];
-                    sa.blocksX[l] = lay.blocksX[l]; sa.blocksY[l] = lay.blocksY[l]; sa.per[l] = lay.per[l];
-                    sa.jobs[l] = sa.jobs[l - 1] + sa.rows * lay.per[l] * lay.blocksX[l] * X265HIP_SADSURF_SUBPEL;
-                }
-                const int waves = (sa.jobs[1] + 3) / 4 + (sa.jobs[2] - sa.jobs[1]) + (sa.jobs[3] - sa.jobs[2]);
-                static const bool xcdOrder = !(getenv("X265HIP_SADSURF_XCD") && !atoi(getenv("X265HIP_SADSURF_XCD")));
-                sa.xcd = xcdOrder ? 1 : 0;
-                const int grid = ((waves / 4 + 1 < 4096 ? waves / 4 + 1 : 4096) + 127) & ~127;
-                static const bool ldsForm = !(getenv("X265HIP_SUBPEL_LDS") && !atoi(getenv("X265HIP_SUBPEL_LDS")));
-                if ((rp->depth == 8 || rp->depth == 10) && ldsForm && rp->stride * rp->B % 4 == 0 && rp->planeElems * rp->B % 4 == 0)
-                {
-                    // a workgroup per 32x32 quadrant of a 64x64 block, per 32x32 block, per four 16x16 blocks (subpel_satd_kernel_lds); a multiple of 128 for the XCD order
-                    const int blocks1 = sa.jobs[1] / X265HIP_SADSURF_SUBPEL, blocks2 = (sa.jobs[2] - sa.jobs[1]) / X265HIP_SADSURF_SUBPEL, blocks3 = (sa.jobs[3] - sa.jobs[2]) / X265HIP_SADSURF_SUBPEL;
-                    const int groups = 4 * blocks3 + blocks2 + (blocks1 + 3) / 4;
-                    // (the entries of the 64x64 blocks are sums over four workgroups: the window kernel in front of this launch has zeroed them, a.subpelOff3)
-                    if (rp->depth == 8)
-                        hipLaunchKernelGGL(subpel_satd_kernel_lds<uint8_t>, dim3(((groups < 16384 ? groups : 16384) + 127) & ~127), dim3(256), 0, st, sa);
-                    else
-                        hipLaunchKernelGGL(subpel_satd_kernel_lds<uint16_t>, dim3(((groups < 16384 ? groups : 16384) + 127) & ~127), dim3(256), 0, st, sa);
-                }
-                else if (rp->depth == 8)
-                    hipLaunchKernelGGL(subpel_satd_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, sa);
-                else
-                    hipLaunchKernelGGL(subpel_satd_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, sa);
-                bad = bad || hipGetLastError() != hipSuccess;
-                // satd W x H = 2 W H B per call
-                span2.bytes += (uint64_t)sa.rows * lay.ctuCols * 3 * 64 * 64 * X265HIP_SADSURF_SUBPEL * 2 * rp->B;
-            }
-            span2.end();
-            for (int k = 0; k < a.nJobs; k++)
-            {
-                // SURVEY.md §8d, "batched exhaustive search of one block over an R x R window counts the unique footprint", applied to what a workgroup
-                // stages: ONE 64x64 source block and ONE (64 + R - 1)^2 window per CTU (R = 2 S; the 16x16 / 32x32 / 64x64 searches of the CTU all read
-                // that one staging, the 32 / 64 SADs are sums of the 16x16 ones), plus the bytes the CTU really emits: a 16 x 16 window of entries and an
-                // origin per block of the levels built (the surfaces themselves never leave LDS; the wide form's region of device memory is working storage, not counted)
-                const int64_t R = 2 * a.job[k].S;
-                span.bytes += (uint64_t)a.job[k].rows * lay.ctuCols * (64 * 64 + (64 + R - 1) * (64 + R - 1)) * rp0->B;
-                for (int l = a.job[k].level0 ? 0 : 1; l < 4; l++)
-                {
-                    int blockRows = 0;
-                    for (int r = a.job[k].row0; r < a.job[k].row0 + a.job[k].rows; r++)
-                        for (int jj = 0; jj < lay.per[l]; jj++)
-                            blockRows += r * lay.per[l] + jj < lay.blocksY[l];
-                    span.bytes += (uint64_t)blockRows * lay.blocksX[l] * (kWin * kWin * lay.entryBytes[l] + 4);
-                }
-            }
-            for (int k = 0; k < a.nJobs && !bad; k++)
-            {
-                x265hip_sadsurf* ss = items[in[k]].ss;
-                const size_t off = (size_t)a.job[k].row0 * lay.pitch, bytes = (size_t)a.job[k].rows * lay.pitch;
-                bad = hipMemcpyAsync(ss->hBuf + off, ss->dBuf + off, bytes, hipMemcpyDeviceToHost, st) != hipSuccess;
-            }
-            const bool synced = hipStreamSynchronize(st) == hipSuccess && !bad;   // (waited for either way: the pooled buffer goes back only when nothing writes it)
-            wide_return(wideBuf);                             // (after a failed synchronisation the reference pictures are failed and nothing launches on them again)
-            if (!synced)
-            {
-                set_error(X265HIP_EHIP, "sadsurf: launch, copy or synchronisation failed");
-                fail_refs(items, g0, g1);
-                (void)hipSetDevice(rp0->device);
-                return;
-            }
-            span.commit();
-            if (span2.bytes) span2.commit();
-            g_statRows += rows;
-            g_statLaunches++;
-            for (int k = 0; k < a.nJobs; k++)
-            {
-                x265hip_sadsurf* ss = items[in[k]].ss;
-                ss->rowsBuilt = upto[k];
-                ss->ctuRowsReady.store(upto[k], std::memory_order_release);
-            }
-            (void)hipSetDevice(rp0->device);
-        }
-        g0 = g1;
-    }
-}
-
-// One workgroup per CTU: a band of one CTU row of one or two surfaces fills a fraction of the chip for the same ~54 us as a full one.  A picture that is
-// still arriving therefore lets its rows wait for company — until the pending CTUs reach X265HIP_SADSURF_BATCH (default 224), the picture is complete, or
-// X265HIP_SADSURF_DEFER bands (default 8) have gone by: the searches of a frame start at least the reference-lag rows behind the band, so nobody is waiting
-// for the newest rows yet; a search that does arrive early measures its candidates on the host, same values (round 4's bench clip: 6 k of 12 million
-// lookups at 2 bands, 20-25 k at 8 and at 16).  True: leave this picture's rows for later.
-static bool rows_wait(x265hip_refpic* rp)
-{
-    static const int batch = getenv("X265HIP_SADSURF_BATCH") ? atoi(getenv("X265HIP_SADSURF_BATCH")) : 224;
-    static const int maxDefer = getenv("X265HIP_SADSURF_DEFER") ? atoi(getenv("X265HIP_SADSURF_DEFER")) : 8;
-    if (batch <= 0)
-        return false;
-    std::vector<x265hip_sadsurf*> list;
-    {
-        std::lock_guard<std::mutex> g(g_ssLock);
-        list = rp->surfaces;
-    }
-    const bool complete = rp->uploaded >= rp->marginY + rp->picH + rp->marginY;
-    int pending = 0;
-    for (x265hip_sadsurf* ss : list)
-        if (ss->ref == rp)
-            pending += (rows_possible(ss) - ss->rowsBuilt) * ss->lay.ctuCols;
-    if (!complete && pending < batch && rp->ssDeferred < maxDefer)
-    {
-        if (pending) rp->ssDeferred++;
-        return true;
-    }
-    rp->ssDeferred = 0;
-    return false;
-}
-
-void sadsurf_rows_arrived(x265hip_refpic* rp)
-{
-    if (!rows_wait(rp))
-        progress_multi(std::vector<x265hip_refpic*>{ rp });
-}
-
-static void free_surface(x265hip_sadsurf* ss)
-{
-    x265hip_srcpic* src = ss->src;
-    {
-        std::lock_guard<std::mutex> g(g_poolLock);
-        g_pool.insert({ { ss->bytes, src->device }, PoolEntry{ ss->dBuf, ss->hBuf } });
-    }
-    delete ss;
-    ::srcpic_unref(src);
-}
-
-// attach jobs that reached the worker together (refpic.hip RefWorker::run): each surface is set up, then the reference pictures concerned make ONE
-// pass of progress_multi — the surfaces of one source picture against its two or three reference pictures share a launch
-void sadsurf_attach_batch(const std::vector<RefJob>& jobs)
-{
-    std::vector<x265hip_refpic*> rps;
-    for (const RefJob& j : jobs)
-    {
-        x265hip_sadsurf* ss = j.ss;
-        // the worker has seen every band queued before this job, so `uploaded` is what the surface can start from
-        if (!ss->ref || j.epoch != ss->ref->epoch.load() || hipSetDevice(ss->ref->device) != hipSuccess)
-            continue;
-        if (ss->src->place != ss->ref->place && !(ss->rep = replica_at(ss->ref, ss->src->place)))
-        {
-            set_error(X265HIP_ENOMEM, "sadsurf: no replica of the reference picture at place %d", ss->src->place);
-            ss->ref->failed = 1;
-            continue;
-        }
-        bool seen = false;
-        for (x265hip_refpic* rp : rps) seen = seen || rp == ss->ref;
-        // together with whatever rows the reference's other surfaces are waiting with (a reference picture that is complete — the usual case —
-        // gives the new surface all its rows at once)
-        if (!seen && !rows_wait(ss->ref)) rps.push_back(ss->ref);
-    }
-    if (!rps.empty())
-        progress_multi(rps);
-}
-
-void sadsurf_job(const RefJob& j)
-{
-    x265hip_sadsurf* ss = j.ss;
-    if (j.kind == 1)
-    {
-        sadsurf_attach_batch(std::vector<RefJob>{ j });
-        return;
-    }
-    // release
-    {
-        std::lock_guard<std::mutex> g(g_ssLock);
-        if (ss->ref)
-        {
-            auto& v = ss->ref->surfaces;
-            for (size_t i = 0; i < v.size(); i++)
-                if (v[i] == ss) { v[i] = v.back(); v.pop_back(); break; }
-            ss->ref = nullptr;
-        }
-    }
-    free_surface(ss);
-}
-
-void sadsurf_detach_all(x265hip_refpic* rp)
-{
-    std::lock_guard<std::mutex> g(g_ssLock);
-    for (x265hip_sadsurf* ss : rp->surfaces)
-        ss->ref = nullptr;
-    rp->surfaces.clear();
+    else if (depth == 8)
+        hipLaunchKernelGGL(subpel_satd_kernel<uint8_t>, dim3(plan::subpel_grid(plan::subpel_waves(sa.jobs))), dim3(256), 0, st, sa);
+    else
+        hipLaunchKernelGGL(subpel_satd_kernel<uint16_t>, dim3(plan::subpel_grid(plan::subpel_waves(sa.jobs))), dim3(256), 0, st, sa);
+    return hipGetLastError() == hipSuccess;
 }
 
 } // namespace xh
-
-using namespace xh;
-
-extern "C" {
-
-static x265hip_srcpic* srcpic_create(int place, int depth, int width, int height);
-
-x265hip_srcpic* x265hip_srcpic_create(int depth, int width, int height)
-{
-    if (ensure_device()) return nullptr;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    return srcpic_create(place_of_device(dev), depth, width, height);
-}
-
-x265hip_srcpic* x265hip_srcpic_create_at(int place, int depth, int width, int height)
-{
-    const int dev = place >= 0 ? place_device(place) : -1;
-    if (dev < 0)
-    {
-        set_error(X265HIP_EINVAL, "x265hip_srcpic_create_at: no place %d (x265hip_places)", place);
-        return nullptr;
-    }
-    int cur = 0;
-    const bool had = hipGetDevice(&cur) == hipSuccess;
-    if (hipSetDevice(dev) != hipSuccess) { set_error(X265HIP_EHIP, "x265hip_srcpic_create_at: hipSetDevice(%d)", dev); return nullptr; }
-    x265hip_srcpic* sp = srcpic_create(place, depth, width, height);
-    if (had) (void)hipSetDevice(cur);
-    return sp;
-}
-
-static x265hip_srcpic* srcpic_create(int place, int depth, int width, int height)
-{
-    if (!valid_depth(depth) || width < 16 || height < 16 || width > 16384 || height > 16384)
-    {
-        set_error(X265HIP_EINVAL, "x265hip_srcpic_create: depth %d %dx%d", depth, width, height);
-        return nullptr;
-    }
-    x265hip_srcpic* sp = new x265hip_srcpic;
-    sp->depth = depth; sp->w = width; sp->h = height;
-    sp->pitch = ((int64_t)width * (depth == 8 ? 1 : 2) + 255) & ~(int64_t)255;
-    (void)hipGetDevice(&sp->device);
-    sp->place = place;
-    const size_t bytes = (size_t)sp->pitch * height;
-    // no stream of its own (3.9 ms each, ~40 source pictures alive in a 1080p encoder): the upload leases one
-    if (hipMalloc((void**)&sp->dLuma, bytes + 256) != hipSuccess ||
-        pinned_alloc((void**)&sp->hStage, bytes) != hipSuccess)
-    {
-        set_error(X265HIP_ENOMEM, "x265hip_srcpic_create: %zu bytes", bytes);
-        x265hip_srcpic_destroy(sp);
-        return nullptr;
-    }
-    return sp;
-}
-
-int x265hip_srcpic_upload(x265hip_srcpic* sp, const void* hostLuma, int64_t stride)
-{
-    if (!sp || !hostLuma || stride < sp->w) return set_error(X265HIP_EINVAL, "x265hip_srcpic_upload: bad arguments");
-    int cur = 0;
-    const bool had = hipGetDevice(&cur) == hipSuccess;
-    int e = check_hip(hipSetDevice(sp->device), "hipSetDevice");
-    if (e) return e;
-    const size_t B = sp->depth == 8 ? 1 : 2;                 // `stride` counts samples, like every stride of the ABI
-    for (int y = 0; y < sp->h; y++)
-        memcpy(sp->hStage + (size_t)y * sp->pitch, (const char*)hostLuma + (size_t)y * stride * B, sp->w * B);
-    hipStream_t st = stream_lease(sp->device);
-    if (!st) e = set_error(X265HIP_EHIP, "x265hip_srcpic_upload: no stream");
-    else
-    {
-        if (!(e = check_hip(hipMemcpyAsync(sp->dLuma, sp->hStage, (size_t)sp->pitch * sp->h, hipMemcpyHostToDevice, st), "srcpic h2d")))
-            e = check_hip(hipStreamSynchronize(st), "srcpic sync");
-        stream_return(sp->device, st);
-    }
-    if (had && cur != sp->device) (void)hipSetDevice(cur);
-    return e;
-}
-
-void x265hip_srcpic_destroy(x265hip_srcpic* sp)
-{
-    if (sp) srcpic_unref(sp);
-}
-
-} // extern "C"
-static void srcpic_unref(x265hip_srcpic* sp)
-{
-    if (sp->refs.fetch_sub(1) != 1) return;
-    int cur = 0;
-    const bool had = hipGetDevice(&cur) == hipSuccess;
-    (void)hipSetDevice(sp->device);
-    if (sp->dLuma) (void)device_free(sp->dLuma);
-    if (sp->hStage) (void)pinned_free(sp->hStage);
-    if (had && cur != sp->device) (void)hipSetDevice(cur);
-    delete sp;
-}
-extern "C" {
-
-x265hip_sadsurf* x265hip_sadsurf_attach(x265hip_srcpic* src, x265hip_refpic* ref, int searchRange, int lambda20)
-{
-    return x265hip_sadsurf_attach_levels(src, ref, searchRange, lambda20, 14);
-}
-
-x265hip_sadsurf* x265hip_sadsurf_attach_levels(x265hip_srcpic* src, x265hip_refpic* ref, int searchRange, int lambda20, int levels)
-{
-    if (ensure_device()) return nullptr;
-    if (!src || !ref || src->depth != ref->depth || src->w != ref->picW || src->h != ref->picH || searchRange < 8 || searchRange > 32 || (searchRange & 3) ||
-        lambda20 < 0 || lambda20 > (1 << 20) || ref->marginX < searchRange + 8 || ref->marginY < searchRange || (levels & ~31) || (levels & 14) != 14 || ((levels & 1) && src->depth != 8))
-    {
-        set_error(X265HIP_EINVAL, "x265hip_sadsurf_attach: pictures do not match, or range %d (8..32, a multiple of 4) / lambda %d / margins out of bounds", searchRange, lambda20);
-        return nullptr;
-    }
-    x265hip_sadsurf* ss = new x265hip_sadsurf;
-    ss->src = src; ss->ref = ref; ss->S = searchRange; ss->lambda20 = lambda20; ss->levels = levels;
-    layout_for(src->w, src->h, src->depth, levels, ss->lay);
-    ss->bytes = (size_t)ss->lay.pitch * ss->lay.ctuRows;
-    {
-        std::lock_guard<std::mutex> g(g_poolLock);
-        auto it = g_pool.find({ ss->bytes, src->device });
-        if (it != g_pool.end()) { ss->dBuf = it->second.d; ss->hBuf = it->second.h; g_pool.erase(it); }
-    }
-    if (!ss->dBuf)
-    {
-        // the table is written by the kernel that runs where the SOURCE picture lives
-        int cur = 0;
-        const bool had = hipGetDevice(&cur) == hipSuccess;
-        (void)hipSetDevice(src->device);
-        const bool ok = hipMalloc((void**)&ss->dBuf, ss->bytes) == hipSuccess && pinned_alloc((void**)&ss->hBuf, ss->bytes) == hipSuccess;
-        if (had && cur != src->device) (void)hipSetDevice(cur);
-        if (!ok)
-        {
-            set_error(X265HIP_ENOMEM, "x265hip_sadsurf_attach: %zu bytes", ss->bytes);
-            if (ss->dBuf) (void)device_free(ss->dBuf);
-            delete ss;
-            return nullptr;
-        }
-    }
-    src->refs.fetch_add(1);
-    memset(&ss->view, 0, sizeof(ss->view));
-    for (int l = 0; l < 4; l++)
-    {
-        x265hip_sadsurf_level& v = ss->view.level[l];
-        if (!(levels >> l & 1))
-            continue;                             // origin == NULL: level not built
-        v.blocksX = ss->lay.blocksX[l]; v.blocksY = ss->lay.blocksY[l]; v.entryBytes = ss->lay.entryBytes[l]; v.blocksPerCtuRow = ss->lay.per[l];
-        v.origin = (const int16_t*)(ss->hBuf + ss->lay.originOff[l]);
-        v.table = ss->hBuf + ss->lay.tableOff[l];
-        v.subpel = ss->lay.subpelOff[l] ? (const uint32_t*)(ss->hBuf + ss->lay.subpelOff[l]) : nullptr;
-    }
-    ss->view.ctuRowPitch = ss->lay.pitch;
-    ss->view.ctuRowsReady = reinterpret_cast<const int*>(&ss->ctuRowsReady);
-    {
-        std::lock_guard<std::mutex> g(g_ssLock);
-        ref->surfaces.push_back(ss);
-    }
-    g_statAttached++;
-    ss->workerPlace = ref->place;                 // the release must queue behind the attach: same worker
-    RefWorker::worker(ref->place).push(RefJob{ ref, 0, ref->epoch.load(), 1, ss });
-    return ss;
-}
-
-const x265hip_sadsurf_view* x265hip_sadsurf_get_view(x265hip_sadsurf* ss) { return ss ? &ss->view : nullptr; }
-
-void x265hip_sadsurf_release(x265hip_sadsurf* ss)
-{
-    if (!ss) return;
-    ss->released = true;
-    RefWorker::worker(ss->workerPlace).push(RefJob{ nullptr, 0, 0, 2, ss });
-}
-
-int x265hip_peer_stats(uint64_t* replicas, uint64_t* bands, uint64_t* bytes)
-{
-    if (replicas) *replicas = g_statReplicas.load();
-    if (bands) *bands = g_statPeerBands.load();
-    if (bytes) *bytes = g_statPeerBytes.load();
-    return X265HIP_OK;
-}
-
-int x265hip_sadsurf_stats(uint64_t* attached, uint64_t* ctuRows, uint64_t* launches, uint64_t* kernelNs)
-{
-    if (kernelNs) (void)x265hip_device_time(X265HIP_CLK_SADSURF, nullptr, kernelNs, nullptr);
-    if (launches) *launches = g_statLaunches.load();
-    if (attached) *attached = g_statAttached.load();
-    if (ctuRows) *ctuRows = g_statRows.load();
-    return X265HIP_OK;
-}
-
-} // extern "C"
