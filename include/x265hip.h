@@ -75,7 +75,8 @@ int  x265hip_peer_stats(uint64_t* replicas, uint64_t* bands, uint64_t* bytes);  
 #define X265HIP_CLK_ENERGY     4   /* source energy planes                                                                             */
 #define X265HIP_CLK_CUSERVE    5   /* CU residual quad-tree jobs (x265hip_cuserve_*)                                                   */
 #define X265HIP_CLK_SUBPEL     6   /* sub-pel SATD tables of the SAD surfaces                                                          */
-#define X265HIP_CLK_COUNT      7
+#define X265HIP_CLK_EDGE       7   /* edge and angle planes of --aq-mode 4 (x265hip_edge_planes)                                       */
+#define X265HIP_CLK_COUNT      8
 /* algorithmicBytes: SURVEY.md §8d bytes of the work inside the spans where the module can state them itself — SAD surfaces: per block of a built CTU
  * the exhaustive search's unique footprint W H B + (W + R - 1)(H + R - 1) B + 4 R^2 (R = 2 searchRange); plane bands: rows x (padded width) x
  * (1 picture + 15 phase planes) x B; 0 for the other clocks (bench.py prices the lookahead searches per 8x8 block from its own count). */
@@ -694,6 +695,21 @@ int x265hip_refpic_wait(x265hip_refpic* rp);        /* blocks until the worker h
  * (row pitch width / 8 * 2).  Host pointers, blocks until the planes are in host memory; one call per plane of a picture entering the
  * encoder.  x265_amd/host/x265_hip_srcplanes.cpp serves cu[].psy_cost_pp from them. */
 int x265hip_source_energy(int depth, const void* hostPlane, int64_t stride, int width, int height, int32_t* hostE8, int32_t* hostE4);
+
+/* ---------------------------------------------------------------- edge and angle planes of a source picture ------- */
+/* What edgeFilter (reference source/encoder/slicetype.cpp:151-215) leaves in Frame::m_edgePic / m_thetaPic for --aq-mode 4: a 5x5 Gaussian / 159, a Sobel
+ * pair on it, magnitude against (pixel)EDGE_THRESHOLD, atan2 in whole degrees; the arithmetic, the reference's quirks included, is stated once in
+ * x265_amd/csrc/edgepass.h.  hostLuma = sample (0, 0) of the picture; rows 0 .. height + 1 and columns 0 .. width + 1 are read as the buffer holds them
+ * (the reference filters row height - 1 and column width - 1 and reads two samples past the picture there), so stride >= width + 2.
+ * edgeOut / thetaOut: host planes of the picture's sample type, width x height written, row pitch outStride samples (what lies between is not touched).
+ * specials[(sign(v) + 1) * 3 + sign(h) + 1]: the angle the reference gives a pixel whose gradients are (h, v) with v == 0, h == 0 or |h| == |v| — made
+ * by the caller with the reference's computeEdge.  A pixel whose angle lies within 2^-10 of a whole degree keeps a provisional value and is listed in
+ * doubts[] as x | y << 16 for the caller to resolve; *doubtCount = how many there are: more than doubtCap means the list is incomplete (not an error: the
+ * caller computes the picture on the host).  The list's order is not defined.  Blocks until the planes are in host memory; stream NULL = the calling
+ * thread's own.  (optional: looked up through a weak reference by x265_amd/host, absent from the CPU emulation of the tests) */
+#define X265HIP_EDGE_SPECIALS 9
+int x265hip_edge_planes(int depth, const void* hostLuma, int64_t stride, int width, int height, const uint16_t specials[X265HIP_EDGE_SPECIALS],
+                        void* edgeOut, void* thetaOut, int64_t outStride, uint32_t* doubts, int doubtCap, int* doubtCount, void* stream);
 
 /* ---------------------------------------------------------------- SAD surfaces (lookup face) ----------------------- */
 /* The integer-pel candidates of MotionEstimate::motionEstimate are sad(fenc, FENC_STRIDE, fref + mx + my * stride, stride) (motion.cpp:246-330

@@ -15,7 +15,12 @@
 //   Yuv::copyPartToYuv      (common/yuv.cpp:155)      a sub-CU's cache is cut out of the CTU's (analysis.cpp:600, ...): child buffer -> position
 // Exactness does not rest on that bookkeeping: before a plane value is used, the block handed to the slot is compared byte for byte with the
 // picture at the claimed position; equal bytes have equal energy.  Anything that does not check out is computed by the C function.
+//
+// The same worker also runs the edge pass of --aq-mode 4 (x265hip_edge_planes): the edge and angle planes that the reference's
+// edgeFilter (encoder/slicetype.cpp:151-215) computes per frame in the pre-lookahead are built when the picture arrives, and the edgeFilter seam at the end
+// of this file copies them into the frame, resolves the listed doubtful angles with the reference's own computeEdge, or calls the reference's body.
 #include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +28,7 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <vector>
 
 #define protected public
 #define private public
@@ -30,11 +36,19 @@
 #include "picyuv.h"
 #include "primitives.h"
 #include "yuv.h"
+#include "frame.h"
+#include "slicetype.h"
 #undef protected
 #undef private
 
 #include "x265hip.h"
 #include "x265_hip_debug.h"
+#include "../csrc/edgepass.h"
+
+// weak: the CPU emulation of the ABI (tests/support) that this object is also linked against does not define it; there it is NULL and every frame's edge
+// planes are computed by the reference's edgeFilter
+extern "C" int x265hip_edge_planes(int depth, const void* hostLuma, int64_t stride, int width, int height, const uint16_t specials[X265HIP_EDGE_SPECIALS],
+                                   void* edgeOut, void* thetaOut, int64_t outStride, uint32_t* doubts, int doubtCap, int* doubtCount, void* stream) __attribute__((weak));
 
 namespace X265_NS {
 
@@ -44,6 +58,7 @@ extern void refCopyFromPicture(PicYuv* self, const x265_picture& pic, const x265
     asm("_ZN4x2659PicYuvRef15copyFromPictureERK12x265_pictureRK10x265_paramii");
 extern void refDestroy(PicYuv* self) asm("_ZN4x2659PicYuvRef7destroyEv");
 void x265hip_refplanes_retire(const pixel* lo);     // x265_hip_refplanes.cpp
+void edgeFilterRef(Frame* curFrame, x265_param* param);   // the reference's body (slicetype_ref.o, compiled with -DedgeFilter=edgeFilterRef)
 bool x265hip_sadplanes_wanted();                    // x265_hip_sadplanes.cpp: source pictures are kept on the device for the SAD surfaces
 extern void refCopyFromPicYuv(Yuv* self, const PicYuv& srcPic, uint32_t cuAddr, uint32_t absPartIdx) asm("_ZN4x2656YuvRef14copyFromPicYuvERKNS_6PicYuvEjj");
 extern void refCopyPartToYuv(const Yuv* self, Yuv& dstYuv, uint32_t absPartIdx) asm("_ZNK4x2656YuvRef13copyPartToYuvERS0_j");
@@ -61,6 +76,12 @@ struct SrcPic                        // one source picture buffer and its energy
     int bw[3], bh[3];                // 8x8 blocks per row / column of each plane
     x265hip_srcpic* dev;             // the luma plane on the device (x265_hip_sadplanes.cpp attaches SAD surfaces to it); version `built`
     int devW, devH;
+    // --aq-mode 4: the edge and angle planes of the picture (edgeW x edgeH samples, row pitch edgeW) and its doubtful pixels; version `edgeBuilt`
+    bool wantEdge;
+    std::mutex edgeLock;             // the buffers below: the worker fills them, the edgeFilter seam copies them out
+    pixel* edge; pixel* theta; uint32_t* doubts;
+    int edgeW, edgeH, doubtCap, doubtCount;
+    std::atomic<uint32_t> edgeBuilt;
 };
 
 const int kMaxPics = 128;
@@ -148,8 +169,106 @@ SrcPic* find_pic(const PicYuv* pic, bool create)
     s.built = 0;
     for (int k = 0; k < 3; k++) { s.e8[k] = s.e4[k] = NULL; s.bw[k] = s.bh[k] = 0; }
     s.dev = NULL; s.devW = s.devH = 0;
+    s.wantEdge = false; s.edge = s.theta = NULL; s.doubts = NULL; s.edgeW = s.edgeH = s.doubtCap = s.doubtCount = 0; s.edgeBuilt = 0;
     g_npics.store(n2 + 1, std::memory_order_release);
     return &s;
+}
+
+// ---- the edge pass of --aq-mode 4
+std::atomic<int> g_edgeState(0);                     // 0 undecided, 1 on, -1 off (switch, missing symbol, device failure)
+std::atomic<uint64_t> g_edgeServed(0), g_edgeKept(0), g_edgeResolved(0);
+uint16_t g_specials[X265HIP_EDGE_SPECIALS];
+// the seam waits here (briefly) for a pass that is queued or under way; on the heap and never destroyed, like the queue below
+struct EdgeSync { std::mutex lock; std::condition_variable cv; };
+EdgeSync& edge_sync() { static EdgeSync* s = new EdgeSync; return *s; }
+void edge_wake()
+{
+    EdgeSync& es = edge_sync();
+    { std::lock_guard<std::mutex> g(es.lock); }
+    es.cv.notify_all();
+}
+
+void edge_report()
+{
+    fprintf(stderr, "x265hip: edgeplanes: %llu frames served, %llu kept on the host, %llu doubtful pixels resolved\n", (unsigned long long)g_edgeServed.load(),
+            (unsigned long long)g_edgeKept.load(), (unsigned long long)g_edgeResolved.load());
+}
+
+// the angle the reference gives the centre of a 3x3 patch of the Gaussian plane: its own computeEdge with height = width = 3
+inline pixel patch_angle(pixel* patch)
+{
+    pixel e[9], t[9];
+    computeEdge(e, patch, t, 3, 3, 3, true);
+    return t[4];
+}
+
+// X265HIP_EDGEPLANES=1 switches the pass on, =0 off; unset: on in the 8-bit build, off in the Main10 / Main12 builds (the measured default:
+// profiles/r13_v1_edgeplanes_ab.txt)
+bool edge_on()
+{
+    int st = g_edgeState.load(std::memory_order_acquire);
+    if (!st)
+    {
+        std::lock_guard<std::mutex> g(g_lock);
+        st = g_edgeState.load();
+        if (!st)
+        {
+            const char* env = getenv("X265HIP_EDGEPLANES");
+            st = (env ? !strcmp(env, "1") : X265_DEPTH == 8) && x265hip_edge_planes ? 1 : -1;
+            // the nine special directions (v == 0, h == 0, |h| == |v|) from the reference itself: gradients (sh * 10, sv * 10)
+            for (int sv = -1; sv <= 1 && st > 0; sv++)
+                for (int sh = -1; sh <= 1; sh++)
+                {
+                    pixel patch[9] = { 0, (pixel)(sv < 0), 0, (pixel)(sh < 0), 0, (pixel)(sh > 0), 0, (pixel)(sv > 0), 0 };
+                    g_specials[(sv + 1) * 3 + sh + 1] = patch_angle(patch);
+                }
+            g_edgeState.store(st, std::memory_order_release);
+        }
+    }
+    return st > 0;
+}
+
+// worker thread, sp->lock held: the planes of the picture now in the buffer
+void build_edge(SrcPic* sp, const PicYuv& pic, uint32_t v)
+{
+    const int w = pic.m_picWidth, h = pic.m_picHeight;
+    if (w > 65535 || h > 65535)
+        return;
+    std::lock_guard<std::mutex> g(sp->edgeLock);
+    if (sp->edgeW != w || sp->edgeH != h)
+    {
+        free(sp->edge); free(sp->theta); free(sp->doubts);
+        sp->doubtCap = w * h / 64 + 256;               // 1.5 % of the picture; noise has 0.2 %, the bench clip 0.3 % (profiles/r13_v1_edgeplanes_ab.txt)
+        sp->edge = (pixel*)malloc((size_t)w * h * sizeof(pixel));
+        sp->theta = (pixel*)malloc((size_t)w * h * sizeof(pixel));
+        sp->doubts = (uint32_t*)malloc((size_t)sp->doubtCap * 4);
+        sp->edgeW = w; sp->edgeH = h;
+    }
+    if (!sp->edge || !sp->theta || !sp->doubts)
+    {
+        sp->edgeW = sp->edgeH = 0;
+        return;
+    }
+    if (x265hip_edge_planes(X265_DEPTH, pic.m_picOrg[0], pic.m_stride, w, h, g_specials, sp->edge, sp->theta, w, sp->doubts, sp->doubtCap, &sp->doubtCount, NULL))
+    {
+        g_edgeState.store(-1);                         // the seam computes every later picture on the host
+        edge_wake();
+        x265hip_device_failure("edgeplanes", "x265hip_edge_planes");
+        return;
+    }
+    sp->edgeBuilt.store(v, std::memory_order_release);
+    edge_wake();
+}
+
+// worker thread: the edge pass of a queued picture, ahead of everything else that is queued — the pre-lookahead asks for these planes as soon as the
+// picture is in the lookahead's input queue, a CTU asks for the energy planes a whole lookahead later
+void edge_first(SrcPic* sp, uint32_t v)
+{
+    std::lock_guard<std::mutex> g(sp->lock);
+    const PicYuv* picp = sp->pic.load();
+    if (!picp || sp->version.load() != v || !sp->wantEdge || g_edgeState.load(std::memory_order_acquire) <= 0 || sp->edgeBuilt.load() == v)
+        return;
+    build_edge(sp, *picp, v);
 }
 
 // the planes of the picture now in the buffer (worker thread: a picture enters the encoder a whole lookahead before its first CTU is analysed)
@@ -224,12 +343,18 @@ void worker()
     for (;;)
     {
         Job j;
+        std::vector<Job> behind;
         {
             std::unique_lock<std::mutex> g(q.lock);
             q.cv.wait(g, [&q] { return !q.jobs.empty(); });
             j = q.jobs.front();
             q.jobs.pop_front();
+            if (g_edgeState.load(std::memory_order_acquire) > 0)
+                behind.assign(q.jobs.begin(), q.jobs.end());
         }
+        edge_first(j.sp, j.version);
+        for (size_t i = 0; i < behind.size(); i++)
+            edge_first(behind[i].sp, behind[i].version);
         build(j.sp, j.version);
     }
 }
@@ -411,7 +536,10 @@ void PicYuv::copyFromPicture(const x265_picture& pic, const x265_param& param, i
     SrcPic* sp = enabled() ? find_pic(this, true) : NULL;
     uint32_t v = 0;
     if (sp)
+    {
         v = sp->version.fetch_add(1) + 1;              // before the pixels change: nobody may trust the old planes from here on
+        sp->wantEdge = param.rc.aqMode == X265_AQ_EDGE && edge_on();
+    }
     refCopyFromPicture(this, pic, param, padx, pady);
     if (sp)
         enqueue(sp, v);                                 // the picture is complete (padding included): its planes are built in the background
@@ -436,6 +564,86 @@ void PicYuv::destroy()
         x265hip_debug_mark("PicYuv::destroy: retired");
     }
     refDestroy(this);
+}
+
+// ---- the edgeFilter seam (weakened in slicetype_seam.o; the call from calcAdaptiveQuantFrame goes through the PLT).  Served: the three full-buffer
+// memsets of the reference (blocks that hang over the right and bottom edges read those zeros), the width x height region of both planes from the
+// worker's buffers, the listed doubtful angles through computeEdge.  Anything else: the reference's body.
+void edgeFilter(Frame* curFrame, x265_param* param)
+{
+    static const bool verbose = getenv("X265HIP_VERBOSE") != NULL, verify = getenv("X265HIP_VERIFY") != NULL;
+    static std::once_flag once;
+    if (verbose)
+        std::call_once(once, [] { atexit(edge_report); });
+    PicYuv* pic = curFrame->m_fencPic;
+    SrcPic* sp = g_state > 0 && edge_on() ? find_pic(pic, false) : NULL;
+    bool served = false;
+    if (sp)
+    {
+        const uint32_t v = sp->version.load();
+        const int w = pic->m_picWidth, h = pic->m_picHeight;
+        if (sp->wantEdge && sp->edgeBuilt.load(std::memory_order_acquire) != v)
+        {
+            // the pass is queued or under way (the pre-lookahead reaches a picture right after it has entered the input queue): worth a wait of up to
+            // 10 ns per pixel — the reference's body takes 21-29 ns per pixel (43-60 ms for a 1080p plane)
+            EdgeSync& es = edge_sync();
+            std::unique_lock<std::mutex> lk(es.lock);
+            es.cv.wait_for(lk, std::chrono::microseconds(500 + (int64_t)w * h / 100), [&] {
+                return sp->edgeBuilt.load(std::memory_order_acquire) == v || g_edgeState.load() <= 0 || sp->version.load() != v; });
+        }
+        std::lock_guard<std::mutex> g(sp->edgeLock);
+        if (sp->pic.load() == pic && sp->edgeBuilt.load(std::memory_order_acquire) == v && sp->edgeW == w && sp->edgeH == h && sp->doubtCount <= sp->doubtCap)
+        {
+            const intptr_t stride = pic->m_stride;
+            const uint32_t numCuInHeight = (h + param->maxCUSize - 1) / param->maxCUSize;
+            const size_t bytes = stride * (numCuInHeight * param->maxCUSize + pic->m_lumaMarginY * 2) * sizeof(pixel);
+            memset(curFrame->m_edgePic, 0, bytes);
+            memset(curFrame->m_gaussianPic, 0, bytes);
+            memset(curFrame->m_thetaPic, 0, bytes);
+            const intptr_t org = pic->m_lumaMarginY * stride + pic->m_lumaMarginX;
+            pixel* edge = curFrame->m_edgePic + org;
+            pixel* theta = curFrame->m_thetaPic + org;
+            for (int r = 0; r < h; r++)
+            {
+                memcpy(edge + r * stride, sp->edge + (size_t)r * w, w * sizeof(pixel));
+                memcpy(theta + r * stride, sp->theta + (size_t)r * w, w * sizeof(pixel));
+            }
+            const pixel* src = pic->m_picOrg[0];
+            for (int i = 0; i < sp->doubtCount; i++)
+            {
+                const int x = xe_doubt_x(sp->doubts[i]), y = xe_doubt_y(sp->doubts[i]);
+                pixel patch[9];
+                for (int j = 0; j < 9; j++)
+                    patch[j] = (pixel)xe_gauss_at(src, (int64_t)stride, x - 1 + j % 3, y - 1 + j / 3, w, h);
+                theta[y * stride + x] = patch_angle(patch);
+            }
+            g_edgeResolved.fetch_add(sp->doubtCount, std::memory_order_relaxed);
+            served = true;
+            if (verify)
+            {
+                pixel* e = (pixel*)malloc(bytes);
+                pixel* t = (pixel*)malloc(bytes);
+                memcpy(e, curFrame->m_edgePic, bytes);
+                memcpy(t, curFrame->m_thetaPic, bytes);
+                edgeFilterRef(curFrame, param);
+                if (memcmp(e, curFrame->m_edgePic, bytes) || memcmp(t, curFrame->m_thetaPic, bytes))
+                {
+                    fprintf(stderr, "x265hip: edgeplanes: VERIFY FAILED: the planes of a %dx%d picture differ from the reference's edgeFilter (%s plane)\n", w, h,
+                            memcmp(e, curFrame->m_edgePic, bytes) ? "edge" : "angle");
+                    abort();
+                }
+                free(e);
+                free(t);
+            }
+        }
+    }
+    if (served)
+        g_edgeServed.fetch_add(1, std::memory_order_relaxed);
+    else
+    {
+        g_edgeKept.fetch_add(1, std::memory_order_relaxed);
+        edgeFilterRef(curFrame, param);
+    }
 }
 
 void Yuv::copyFromPicYuv(const PicYuv& srcPic, uint32_t cuAddr, uint32_t absPartIdx)
