@@ -76,7 +76,8 @@ int  x265hip_peer_stats(uint64_t* replicas, uint64_t* bands, uint64_t* bytes);  
 #define X265HIP_CLK_CUSERVE    5   /* CU residual quad-tree jobs (x265hip_cuserve_*)                                                   */
 #define X265HIP_CLK_SUBPEL     6   /* sub-pel SATD tables of the SAD surfaces                                                          */
 #define X265HIP_CLK_EDGE       7   /* edge and angle planes of --aq-mode 4 (x265hip_edge_planes)                                       */
-#define X265HIP_CLK_COUNT      8
+#define X265HIP_CLK_SCENE      8   /* histograms of --hist-scenecut and edge bits of --rskip 2 (x265hip_scene_stats)                   */
+#define X265HIP_CLK_COUNT      9
 /* algorithmicBytes: SURVEY.md §8d bytes of the work inside the spans where the module can state them itself — SAD surfaces: per block of a built CTU
  * the exhaustive search's unique footprint W H B + (W + R - 1)(H + R - 1) B + 4 R^2 (R = 2 searchRange); plane bands: rows x (padded width) x
  * (1 picture + 15 phase planes) x B; 0 for the other clocks (bench.py prices the lookahead searches per 8x8 block from its own count). */
@@ -710,6 +711,35 @@ int x265hip_source_energy(int depth, const void* hostPlane, int64_t stride, int 
 #define X265HIP_EDGE_SPECIALS 9
 int x265hip_edge_planes(int depth, const void* hostLuma, int64_t stride, int width, int height, const uint16_t specials[X265HIP_EDGE_SPECIALS],
                         void* edgeOut, void* thetaOut, int64_t outStride, uint32_t* doubts, int doubtCap, int* doubtCount, void* stream);
+
+/* ---------------------------------------------------------------- scene statistics of a source picture -------------- */
+/* What Encoder::computeHistograms (reference source/encoder/encoder.cpp:1361-1487) computes per input picture of a --hist-scenecut encode, and what the
+ * computeEdge call of FrameEncoder::compressFrame (frameencoder.cpp:451-461) computes per frame of a --rskip 2 encode: the 0 / 1 edge plane of the SOURCE
+ * luma (a Sobel pair, magnitude against (pixel)EDGE_THRESHOLD; no Gaussian, no angle), the two edge bins, and exact histograms of Y, U and V.  All of it
+ * is integer; the arithmetic is stated once in x265_amd/csrc/scenestats.h (and edgepass.h).
+ * depth = the build's X265_DEPTH.  numPlanes = 1 or 3 host planes of sampleBytes-wide samples (1 or 2), plane k widths[k] x heights[k], row pitch
+ * strides[k] SAMPLES.  Every sample is converted first, as computeHistograms does it (conv / shift / mask):
+ *   X265HIP_CONV_NONE      the sample itself (sampleBytes must be the build's pixel size; NOT masked, as in the reference)
+ *   X265HIP_CONV_SHL       sample << shift                (8-bit samples into a 16-bit build, planecopy_cp)
+ *   X265HIP_CONV_SHR_MASK  (sample >> shift) & mask       (planecopy_sp)
+ *   X265HIP_CONV_SHL_MASK  (sample << shift) & mask       (planecopy_sp_shl)
+ * wantHist: yuvHist[numPlanes][bins] receives the histograms, bins = 256 at depth 8 and 1024 at depth 10 (HISTOGRAM_BINS); depth 12 is refused — its
+ * 4096 values do not fit the reference's own 1024 bins.  A converted sample >= bins is a range error (the reference indexes past its array): they are
+ * counted in *rangeErrors, and when that is non-zero every other output is unspecified.  Without wantHist only plane 0 is read (numPlanes = 1), and
+ * *rangeErrors is 0.
+ * edgeBits (NULL = not wanted): a host plane of the build's pixel type, row pitch edgeStride samples; rows 1 .. height - 2, columns 1 .. width - 2 are
+ * written (1 = edge, 0 = none).  The border ring and what lies between the rows are NOT touched: computeEdge does not write them, and what they hold is the
+ * caller's business (computeHistograms has zeroed the plane, Frame::m_edgeBitPic keeps its bytes).
+ * edgeHist (NULL = not wanted): [1] = the number of edge pixels, [0] = widths[0] * heights[0] - [1].
+ * Blocks until the outputs are in host memory; stream NULL = the calling thread's own.  (optional: looked up through a weak reference by x265_amd/host,
+ * absent from the CPU emulation of the tests) */
+#define X265HIP_CONV_NONE      0
+#define X265HIP_CONV_SHL       1
+#define X265HIP_CONV_SHR_MASK  2
+#define X265HIP_CONV_SHL_MASK  3
+int x265hip_scene_stats(int depth, int numPlanes, const void* const* hostPlanes, const int* widths, const int* heights, const int64_t* strides,
+                        int sampleBytes, int conv, int shift, int mask, int wantHist, void* edgeBits, int64_t edgeStride,
+                        int32_t* edgeHist, int32_t* yuvHist, uint32_t* rangeErrors, void* stream);
 
 /* ---------------------------------------------------------------- SAD surfaces (lookup face) ----------------------- */
 /* The integer-pel candidates of MotionEstimate::motionEstimate are sad(fenc, FENC_STRIDE, fref + mx + my * stride, stride) (motion.cpp:246-330

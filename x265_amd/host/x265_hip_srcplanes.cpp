@@ -19,6 +19,8 @@
 // The same worker also runs the edge pass of --aq-mode 4 (x265hip_edge_planes): the edge and angle planes that the reference's
 // edgeFilter (encoder/slicetype.cpp:151-215) computes per frame in the pre-lookahead are built when the picture arrives, and the edgeFilter seam at the end
 // of this file copies them into the frame, resolves the listed doubtful angles with the reference's own computeEdge, or calls the reference's body.
+// And the edge bits of --rskip 2 (x265hip_scene_stats): the 0 / 1 plane that FrameEncoder::compressFrame (frameencoder.cpp:451-461) has
+// computeEdge write into Frame::m_edgeBitPic before the frame's first CTU row starts is built when the picture arrives; the computeEdge seam copies it in.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -43,12 +45,17 @@
 
 #include "x265hip.h"
 #include "x265_hip_debug.h"
-#include "../csrc/edgepass.h"
+#include "../csrc/scenestats.h"
 
 // weak: the CPU emulation of the ABI (tests/support) that this object is also linked against does not define it; there it is NULL and every frame's edge
 // planes are computed by the reference's edgeFilter
 extern "C" int x265hip_edge_planes(int depth, const void* hostLuma, int64_t stride, int width, int height, const uint16_t specials[X265HIP_EDGE_SPECIALS],
                                    void* edgeOut, void* thetaOut, int64_t outStride, uint32_t* doubts, int doubtCap, int* doubtCount, void* stream) __attribute__((weak));
+
+// weak, for the same reason: there every frame's edge bits are computed by the reference's computeEdge
+extern "C" int x265hip_scene_stats(int depth, int numPlanes, const void* const* hostPlanes, const int* widths, const int* heights, const int64_t* strides,
+                                   int sampleBytes, int conv, int shift, int mask, int wantHist, void* edgeBits, int64_t edgeStride,
+                                   int32_t* edgeHist, int32_t* yuvHist, uint32_t* rangeErrors, void* stream) __attribute__((weak));
 
 namespace X265_NS {
 
@@ -59,6 +66,8 @@ extern void refCopyFromPicture(PicYuv* self, const x265_picture& pic, const x265
 extern void refDestroy(PicYuv* self) asm("_ZN4x2659PicYuvRef7destroyEv");
 void x265hip_refplanes_retire(const pixel* lo);     // x265_hip_refplanes.cpp
 void edgeFilterRef(Frame* curFrame, x265_param* param);   // the reference's body (slicetype_ref.o, compiled with -DedgeFilter=edgeFilterRef)
+// likewise (-DcomputeEdge=computeEdgeRef); edgeFilterRef calls this one
+bool computeEdgeRef(pixel* edgePic, pixel* refPic, pixel* edgeTheta, intptr_t stride, int height, int width, bool bcalcTheta, pixel whitePixel);
 bool x265hip_sadplanes_wanted();                    // x265_hip_sadplanes.cpp: source pictures are kept on the device for the SAD surfaces
 extern void refCopyFromPicYuv(Yuv* self, const PicYuv& srcPic, uint32_t cuAddr, uint32_t absPartIdx) asm("_ZN4x2656YuvRef14copyFromPicYuvERKNS_6PicYuvEjj");
 extern void refCopyPartToYuv(const Yuv* self, Yuv& dstYuv, uint32_t absPartIdx) asm("_ZNK4x2656YuvRef13copyPartToYuvERS0_j");
@@ -82,6 +91,12 @@ struct SrcPic                        // one source picture buffer and its energy
     pixel* edge; pixel* theta; uint32_t* doubts;
     int edgeW, edgeH, doubtCap, doubtCount;
     std::atomic<uint32_t> edgeBuilt;
+    // --rskip 2 without --hist-scenecut and without --aq-mode 4: the 0 / 1 edge plane of the picture (bitsW x bitsH samples, row pitch bitsW; the ring is
+    // not defined); version `bitsBuilt`.  Under edgeLock too
+    bool wantBits;
+    pixel* bits;
+    int bitsW, bitsH;
+    std::atomic<uint32_t> bitsBuilt;
 };
 
 const int kMaxPics = 128;
@@ -170,6 +185,7 @@ SrcPic* find_pic(const PicYuv* pic, bool create)
     for (int k = 0; k < 3; k++) { s.e8[k] = s.e4[k] = NULL; s.bw[k] = s.bh[k] = 0; }
     s.dev = NULL; s.devW = s.devH = 0;
     s.wantEdge = false; s.edge = s.theta = NULL; s.doubts = NULL; s.edgeW = s.edgeH = s.doubtCap = s.doubtCount = 0; s.edgeBuilt = 0;
+    s.wantBits = false; s.bits = NULL; s.bitsW = s.bitsH = 0; s.bitsBuilt = 0;
     g_npics.store(n2 + 1, std::memory_order_release);
     return &s;
 }
@@ -260,15 +276,74 @@ void build_edge(SrcPic* sp, const PicYuv& pic, uint32_t v)
     edge_wake();
 }
 
+// ---- the edge bits of --rskip 2
+std::atomic<int> g_bitsState(0);                     // 0 undecided, 1 on, -1 off (switch, missing symbol, device failure)
+std::atomic<uint64_t> g_bitsServed(0), g_bitsKept(0);
+
+void bits_report()
+{
+    fprintf(stderr, "x265hip: edgebits: %llu frames served, %llu kept on the host\n", (unsigned long long)g_bitsServed.load(), (unsigned long long)g_bitsKept.load());
+}
+
+// X265HIP_SCENESTATS=1 switches the pass on, =0 off (the switch of the --hist-scenecut seam, x265_hip_scenecut.cpp); unset: off in every build — measured
+// inside the off leg's span in the 8-bit and Main10 builds, not measured in the Main12 build (profiles/r14_v1_scenestats_ab.txt)
+bool bits_on()
+{
+    int st = g_bitsState.load(std::memory_order_acquire);
+    if (!st)
+    {
+        const char* env = getenv("X265HIP_SCENESTATS");
+        st = (env ? !strcmp(env, "1") : false) && x265hip_scene_stats ? 1 : -1;
+        g_bitsState.store(st, std::memory_order_release);
+    }
+    return st > 0;
+}
+
+// worker thread, sp->lock held: the bit plane of the picture now in the buffer
+void build_bits(SrcPic* sp, const PicYuv& pic, uint32_t v)
+{
+    const int w = pic.m_picWidth, h = pic.m_picHeight;
+    if (w > 65535 || h > 65535 || w < 3 || h < 3)
+        return;
+    std::lock_guard<std::mutex> g(sp->edgeLock);
+    if (sp->bitsW != w || sp->bitsH != h)
+    {
+        free(sp->bits);
+        sp->bits = (pixel*)malloc((size_t)w * h * sizeof(pixel));
+        sp->bitsW = w; sp->bitsH = h;
+    }
+    if (!sp->bits)
+    {
+        sp->bitsW = sp->bitsH = 0;
+        return;
+    }
+    const void* plane = pic.m_picOrg[0];
+    const int64_t stride = pic.m_stride;
+    uint32_t outOfRange = 0;
+    if (x265hip_scene_stats(X265_DEPTH, 1, &plane, &w, &h, &stride, (int)sizeof(pixel), X265HIP_CONV_NONE, 0, (1 << X265_DEPTH) - 1, 0, sp->bits, w, NULL, NULL,
+                            &outOfRange, NULL))
+    {
+        g_bitsState.store(-1);                         // the seam computes every later picture on the host
+        edge_wake();
+        x265hip_device_failure("edgebits", "x265hip_scene_stats");
+        return;
+    }
+    sp->bitsBuilt.store(v, std::memory_order_release);
+    edge_wake();
+}
+
 // worker thread: the edge pass of a queued picture, ahead of everything else that is queued — the pre-lookahead asks for these planes as soon as the
 // picture is in the lookahead's input queue, a CTU asks for the energy planes a whole lookahead later
 void edge_first(SrcPic* sp, uint32_t v)
 {
     std::lock_guard<std::mutex> g(sp->lock);
     const PicYuv* picp = sp->pic.load();
-    if (!picp || sp->version.load() != v || !sp->wantEdge || g_edgeState.load(std::memory_order_acquire) <= 0 || sp->edgeBuilt.load() == v)
+    if (!picp || sp->version.load() != v)
         return;
-    build_edge(sp, *picp, v);
+    if (sp->wantEdge && g_edgeState.load(std::memory_order_acquire) > 0 && sp->edgeBuilt.load() != v)
+        build_edge(sp, *picp, v);
+    if (sp->wantBits && g_bitsState.load(std::memory_order_acquire) > 0 && sp->bitsBuilt.load() != v)
+        build_bits(sp, *picp, v);
 }
 
 // the planes of the picture now in the buffer (worker thread: a picture enters the encoder a whole lookahead before its first CTU is analysed)
@@ -349,7 +424,7 @@ void worker()
             q.cv.wait(g, [&q] { return !q.jobs.empty(); });
             j = q.jobs.front();
             q.jobs.pop_front();
-            if (g_edgeState.load(std::memory_order_acquire) > 0)
+            if (g_edgeState.load(std::memory_order_acquire) > 0 || g_bitsState.load(std::memory_order_acquire) > 0)
                 behind.assign(q.jobs.begin(), q.jobs.end());
         }
         edge_first(j.sp, j.version);
@@ -539,6 +614,7 @@ void PicYuv::copyFromPicture(const x265_picture& pic, const x265_param& param, i
     {
         v = sp->version.fetch_add(1) + 1;              // before the pixels change: nobody may trust the old planes from here on
         sp->wantEdge = param.rc.aqMode == X265_AQ_EDGE && edge_on();
+        sp->wantBits = param.recursionSkipMode == EDGE_BASED_RSKIP && !param.bHistBasedSceneCut && param.rc.aqMode != X265_AQ_EDGE && bits_on();
     }
     refCopyFromPicture(this, pic, param, padx, pady);
     if (sp)
@@ -644,6 +720,72 @@ void edgeFilter(Frame* curFrame, x265_param* param)
         g_edgeKept.fetch_add(1, std::memory_order_relaxed);
         edgeFilterRef(curFrame, param);
     }
+}
+
+// ---- the computeEdge seam (weakened in slicetype_seam.o; its body stays reachable as computeEdgeRef).  Served: the call of FrameEncoder::compressFrame for
+// --rskip 2 — no angles, whitePixel 1, refPic the luma origin of a registered source picture whose bit plane of the current version is built: rows
+// 1 .. height - 2, columns 1 .. width - 2 are copied, so the ring of m_edgeBitPic keeps its bytes as the reference leaves it.  Every other call — the 3x3
+// patches of the edge pass above, edgeFilter's, the one of an unserved computeHistograms — goes straight to the reference's body.
+bool computeEdge(pixel* edgePic, pixel* refPic, pixel* edgeTheta, intptr_t stride, int height, int width, bool bcalcTheta, pixel whitePixel)
+{
+    SrcPic* sp = NULL;
+    if (!bcalcTheta && whitePixel == 1 && edgePic && refPic && g_state > 0)
+    {
+        const int n = g_npics.load(std::memory_order_acquire);
+        for (int i = 0; i < n && !sp; i++)
+        {
+            const PicYuv* p = g_pics[i].pic.load(std::memory_order_relaxed);
+            if (p && p->m_picOrg[0] == refPic && (int)p->m_picWidth == width && (int)p->m_picHeight == height && p->m_stride == stride)
+                sp = &g_pics[i];
+        }
+    }
+    if (!sp)
+        return computeEdgeRef(edgePic, refPic, edgeTheta, stride, height, width, bcalcTheta, whitePixel);
+    static const bool verbose = getenv("X265HIP_VERBOSE") != NULL, verify = getenv("X265HIP_VERIFY") != NULL;
+    static std::once_flag once;
+    if (verbose)
+        std::call_once(once, [] { atexit(bits_report); });
+    bool served = false;
+    if (bits_on() && sp->wantBits)
+    {
+        const uint32_t v = sp->version.load();
+        if (sp->bitsBuilt.load(std::memory_order_acquire) != v)
+        {
+            // the picture has been in the encoder for a whole lookahead: a pass that is still queued or under way is rare, and worth a wait of up to 2 ns per
+            // pixel — less than the edgeFilter seam allows itself, as the body it replaces is cheaper (no Gaussian, no angle)
+            EdgeSync& es = edge_sync();
+            std::unique_lock<std::mutex> lk(es.lock);
+            es.cv.wait_for(lk, std::chrono::microseconds(200 + (int64_t)width * height / 500), [&] {
+                return sp->bitsBuilt.load(std::memory_order_acquire) == v || g_bitsState.load() <= 0 || sp->version.load() != v; });
+        }
+        std::lock_guard<std::mutex> g(sp->edgeLock);
+        if (sp->bitsBuilt.load(std::memory_order_acquire) == v && sp->version.load() == v && sp->bitsW == width && sp->bitsH == height)
+        {
+            for (int r = 1; r < height - 1; r++)
+                memcpy(edgePic + r * stride + 1, sp->bits + (size_t)r * width + 1, (size_t)(width - 2) * sizeof(pixel));
+            served = true;
+            if (verify)
+            {
+                pixel* want = (pixel*)malloc((size_t)stride * height * sizeof(pixel));
+                bool same = want && computeEdgeRef(want, refPic, NULL, stride, height, width, false, 1);
+                for (int r = 1; same && r < height - 1; r++)
+                    same = !memcmp(want + r * stride + 1, edgePic + r * stride + 1, (size_t)(width - 2) * sizeof(pixel));
+                if (!same)
+                {
+                    fprintf(stderr, "x265hip: edgebits: VERIFY FAILED: the edge bits of a %dx%d picture differ from the reference's computeEdge\n", width, height);
+                    abort();
+                }
+                free(want);
+            }
+        }
+    }
+    if (served)
+    {
+        g_bitsServed.fetch_add(1, std::memory_order_relaxed);
+        return true;
+    }
+    g_bitsKept.fetch_add(1, std::memory_order_relaxed);
+    return computeEdgeRef(edgePic, refPic, edgeTheta, stride, height, width, bcalcTheta, whitePixel);
 }
 
 void Yuv::copyFromPicYuv(const PicYuv& srcPic, uint32_t cuAddr, uint32_t absPartIdx)
