@@ -77,7 +77,8 @@ int  x265hip_peer_stats(uint64_t* replicas, uint64_t* bands, uint64_t* bytes);  
 #define X265HIP_CLK_SUBPEL     6   /* sub-pel SATD tables of the SAD surfaces                                                          */
 #define X265HIP_CLK_EDGE       7   /* edge and angle planes of --aq-mode 4 (x265hip_edge_planes)                                       */
 #define X265HIP_CLK_SCENE      8   /* histograms of --hist-scenecut and edge bits of --rskip 2 (x265hip_scene_stats)                   */
-#define X265HIP_CLK_COUNT      9
+#define X265HIP_CLK_PICHASH    9   /* CRC / checksum picture hashes of --hash 2 / 3 (x265hip_picture_hash)                             */
+#define X265HIP_CLK_COUNT      10
 /* algorithmicBytes: SURVEY.md §8d bytes of the work inside the spans where the module can state them itself — SAD surfaces: per block of a built CTU
  * the exhaustive search's unique footprint W H B + (W + R - 1)(H + R - 1) B + 4 R^2 (R = 2 searchRange); plane bands: rows x (padded width) x
  * (1 picture + 15 phase planes) x B; 0 for the other clocks (bench.py prices the lookahead searches per 8x8 block from its own count). */
@@ -740,6 +741,22 @@ int x265hip_edge_planes(int depth, const void* hostLuma, int64_t stride, int wid
 int x265hip_scene_stats(int depth, int numPlanes, const void* const* hostPlanes, const int* widths, const int* heights, const int64_t* strides,
                         int sampleBytes, int conv, int shift, int mask, int wantHist, void* edgeBits, int64_t edgeStride,
                         int32_t* edgeHist, int32_t* yuvHist, uint32_t* rangeErrors, void* stream);
+
+/* ---------------------------------------------------------------- decoded-picture hashes of a reconstructed picture -- */
+/* What updateCRC and updateChecksum (reference source/common/picyuv.cpp:507-571) add to the running values of the decoded-picture-hash SEI of --hash 2 / 3
+ * for a band of rows of a reconstructed picture (FrameEncoder::initDecodedPictureHashSEI, frameencoder.cpp:1167-1237: one band per finished CTU row, or
+ * the whole picture with --slices > 1).  Integer and exact: the checksum is a sum mod 2^32; the CRC (16 bits, polynomial 0x1021, augmented form) of a band
+ * of N bits entered with state s is s x^N + M(x) mod P, so the parts are hashed from state 0 in parallel and combined.  The arithmetic is stated once in
+ * x265_amd/csrc/pichash.h.
+ * depth = the build's X265_DEPTH (8: 1-byte samples; 10 / 12: 2-byte samples, low byte hashed first).  method = 2 (CRC) or 3 (checksum); MD5 (1) is one
+ * serial chain and is refused.  planes[k], k < numPlanes (1..3): host memory, `plane` = the first sample of the band's first row, stride in samples
+ * (>= width; what lies between the rows is not read), width x height >= 1 x 1 samples of any width, y0 = the picture row of the band's first row (it enters
+ * the checksum's mask; the CRC ignores it).  state[k]: in, the running value of plane k before the band (CRC: its low 16 bits); out, the value after it.
+ * Entries of state beyond numPlanes are not touched, and a refused or failed call leaves all of state as it was.
+ * The call stages the bands itself (page-locked, per calling thread: it is reentrant) and blocks until state is written; stream NULL = the calling
+ * thread's own.  (optional: looked up through a weak reference by x265_amd/host, absent from the CPU emulation of the tests) */
+typedef struct { const void* plane; int64_t stride; int32_t width, height, y0; } x265hip_hash_plane;
+int x265hip_picture_hash(int depth, int method, const x265hip_hash_plane* planes, int numPlanes, uint32_t* state, void* stream);
 
 /* ---------------------------------------------------------------- SAD surfaces (lookup face) ----------------------- */
 /* The integer-pel candidates of MotionEstimate::motionEstimate are sad(fenc, FENC_STRIDE, fref + mx + my * stride, stride) (motion.cpp:246-330

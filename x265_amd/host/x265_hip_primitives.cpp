@@ -580,7 +580,7 @@ static void report_calls()
 // X265HIP_VERBOSE: the device-time ledger of the bound modules (include/x265hip.h, x265hip_device_time) — what the GPU was busy with, in total
 static void report_device_time()
 {
-    static const char* const names[X265HIP_CLK_COUNT] = { "lookahead searches", "other lookahead kernels", "sub-pel plane bands", "SAD surfaces", "source energy planes", "CU residual quad-tree jobs", "sub-pel SATD tables", "edge and angle planes", "scene statistics" };
+    static const char* const names[X265HIP_CLK_COUNT] = { "lookahead searches", "other lookahead kernels", "sub-pel plane bands", "SAD surfaces", "source energy planes", "CU residual quad-tree jobs", "sub-pel SATD tables", "edge and angle planes", "scene statistics", "picture hashes" };
     uint64_t total = 0;
     char line[1024];
     int n = 0;
@@ -589,8 +589,8 @@ static void report_device_time()
         uint64_t spans = 0, ns = 0, bytes = 0;
         x265hip_device_time(c, &spans, &ns, &bytes);
         total += ns;
-        if ((c == X265HIP_CLK_EDGE || c == X265HIP_CLK_SCENE) && !spans)
-            continue;                                   // only --aq-mode 4 / --hist-scenecut / --rskip 2 encodes have these clocks: every other encode prints the line it always printed
+        if ((c == X265HIP_CLK_EDGE || c == X265HIP_CLK_SCENE || c == X265HIP_CLK_PICHASH) && !spans)
+            continue;                                   // only --aq-mode 4 / --hist-scenecut / --rskip 2 / --hash 2, 3 encodes have these clocks: every other encode prints the line it always printed
         n += snprintf(line + n, sizeof(line) - n, "%s%s %.3f ms in %llu launch groups (%llu algorithmic bytes)", c ? ", " : "", names[c], ns * 1e-6,
                       (unsigned long long)spans, (unsigned long long)bytes);
     }

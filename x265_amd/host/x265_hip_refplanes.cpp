@@ -417,9 +417,25 @@ void x265hip_install_lookup_slots(EncoderPrimitives& p)
     LOOKUP_PU(64, 16); LOOKUP_PU(16, 64);
 }
 
+// The picture-hash seam (x265_hip_pichash.cpp) is a unit of the product's encoders only.  In an encoder linked without it the body below
+// hashes every row of a --hash 2 / 3 encode with the reference's own code; asked for the seam (X265HIP_PICHASH=1) such an encoder says so in the seam's words.
+extern "C" void x265hip_pichash_linked() __attribute__((weak));
+static std::atomic<uint64_t> g_hashRowsKept(0);
+static void hash_row_without_seam(const x265_param* p)
+{
+    static const bool report = getenv("X265HIP_VERBOSE") && getenv("X265HIP_PICHASH") && !strcmp(getenv("X265HIP_PICHASH"), "1");
+    if (!report || p->maxSlices != 1 || (p->decodedPictureHashSEI != 2 && p->decodedPictureHashSEI != 3))
+        return;
+    static std::once_flag once;
+    std::call_once(once, [] { atexit([] { fprintf(stderr, "x265hip: pichash: 0 rows served, %llu kept on the host\n", (unsigned long long)g_hashRowsKept.load()); }); });
+    g_hashRowsKept.fetch_add(1, std::memory_order_relaxed);
+}
+
 void FrameFilter::processPostRow(int row)
 {
     Mirror* m = NULL;
+    if (!x265hip_pichash_linked)
+        hash_row_without_seam(m_param);
     // X265HIP_DEBUG_DELAY_US=n: sleep n microseconds here, seams on or off.  A diagnostic: the reference encoder's own output depends on thread
     // timing in a few corner configurations (tools/fuzz_encoder.py uses this to tell those from real mismatches)
     static const int delayUs = getenv("X265HIP_DEBUG_DELAY_US") ? atoi(getenv("X265HIP_DEBUG_DELAY_US")) : 0;
