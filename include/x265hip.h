@@ -758,6 +758,34 @@ int x265hip_scene_stats(int depth, int numPlanes, const void* const* hostPlanes,
 typedef struct { const void* plane; int64_t stride; int32_t width, height, y0; } x265hip_hash_plane;
 int x265hip_picture_hash(int depth, int method, const x265hip_hash_plane* planes, int numPlanes, uint32_t* state, void* stream);
 
+/* ---------------------------------------------------------------- the frame encoder's weighted-prediction analysis -- */
+/* What weightAnalyse (reference source/encoder/weightPrediction.cpp:222-505; FrameEncoder::compressFrame calls it for every P slice with --weightp and every
+ * B slice with --weightb) MEASURES once its early-termination test has not fired: per plane a motion-compensated copy of the reference (mcLuma :60-89 over
+ * the four lowres planes, mcChroma :93-163 over the full-resolution source chroma) and, per candidate weight, weightCost (:169-218): weight_pp over the plane
+ * and the sum over its blocks of min(satd 8x8, intraCost) (luma), satd 8x8 (4:2:0 / 4:2:2 chroma) or satd 16x16 (4:4:4 chroma).  Integer and exact; the
+ * arithmetic is stated once in x265_amd/csrc/wpcost.h.  The decisions around the measurements (float guesses, loops, thresholds) stay with the caller.
+ *   begin      depth = the build's X265_DEPTH (8: 1-byte samples; 10 / 12: 2-byte), csp = X265_CSP_I400..I444 (0..3).  A context serves one thread at a time.
+ *   set_luma   host memory, strides in samples: fencPlane = the frame's lowresPlane[0], refPlanes = the reference's lowresPlane[0..3] (only [0] is read with
+ *              mvs NULL: no compensation), sample (0, 0) each, readable 8 samples / rows before and 16 after width / lines; width, lines multiples of 8;
+ *              intraCost: (width / 8) * (lines / 8) entries; mvs: as many (x, y) int32 pairs, quarter-pels, or NULL.
+ *   set_chroma plane 1 / 2: fencPlane / refPlane = the pictures' chroma planes, readable 9 before and (16 >> the chroma shift) + 10 after; width, height = the reference's clamped
+ *              extents (multiples of 16 >> the chroma shifts); mvs: the same lowres vectors (lowresWidthInCU * lowresHeightInCU pairs) or NULL.
+ *   Both upload the planes whole, launch the compensation once and return without waiting; they replace what the plane held before.
+ *   eval       1..16 candidates in one launch; wtPresent == 0 is the unweighted pass.  blockCosts (may be NULL): [n][x265hip_wpcost_blocks(ctx, plane)] in
+ *              weightCost's block order; totals[n] = their sums mod 2^32.  Blocks until both are written.
+ *   stats      launches, device time and uploaded bytes of the context so far.
+ * (optional: looked up through weak references by x265_amd/host, absent from the CPU emulation of the tests) */
+typedef struct x265hip_wpcost x265hip_wpcost;
+int x265hip_wpcost_begin(int depth, int csp, x265hip_wpcost** ctx);
+int x265hip_wpcost_set_luma(x265hip_wpcost* ctx, const void* fencPlane, const void* const refPlanes[4], int64_t stride, int width, int lines,
+                            const int32_t* intraCost, const int32_t* mvs);
+int x265hip_wpcost_set_chroma(x265hip_wpcost* ctx, int plane, const void* fencPlane, const void* refPlane, int64_t stride, int width, int height,
+                              const int32_t* mvs, int lowresWidthInCU, int lowresHeightInCU);
+int x265hip_wpcost_blocks(const x265hip_wpcost* ctx, int plane);
+int x265hip_wpcost_eval(x265hip_wpcost* ctx, int plane, const x265hip_weight_param* cand, int n, uint32_t* blockCosts, uint32_t* totals);
+void x265hip_wpcost_stats(const x265hip_wpcost* ctx, uint64_t* launches, uint64_t* deviceNs, uint64_t* uploadedBytes);
+void x265hip_wpcost_end(x265hip_wpcost* ctx);
+
 /* ---------------------------------------------------------------- SAD surfaces (lookup face) ----------------------- */
 /* The integer-pel candidates of MotionEstimate::motionEstimate are sad(fenc, FENC_STRIDE, fref + mx + my * stride, stride) (motion.cpp:246-330
  * macros; HEX :770-944, STAR :1132-1240) with fenc a copy of the SOURCE picture's PU (setSourcePU, :194-222) and fref the finished reference

@@ -46,13 +46,14 @@ def main():
     ap.add_argument("--bits", type=int, default=8, help="encoder build: 8, 10 or 12 (x265_<bits>bit / x265_hip_<bits>bit); the clip stays 8-bit input")
     ap.add_argument("--csp", default="i420", help="chroma format of the clip and the encode: i420, i422, i444 (--input-csp)")
     ap.add_argument("--input-depth", type=int, default=8, help="10: the clip holds 16-bit samples with 10 significant bits")
+    ap.add_argument("--fade", action="store_true", help="the clip fades in from 40 %% to full brightness (make_clip(fade=True)): weighted prediction has something to find")
     a = ap.parse_args()
     w, h = map(int, a.res.split("x"))
     from x265_amd.synth import make_clip
     other = a.csp != "i420" or a.input_depth != 8
-    clip = "/tmp/ab_clip_%dx%d_%d%s.yuv" % (w, h, a.frames, "_%s_d%d" % (a.csp, a.input_depth) if other else "")
+    clip = "/tmp/ab_clip_%dx%d_%d%s%s.yuv" % (w, h, a.frames, "_%s_d%d" % (a.csp, a.input_depth) if other else "", "_fade" if a.fade else "")
     if not os.path.exists(clip):
-        make_clip(clip, w, h, a.frames, seed=4321, csp=a.csp, depth=a.input_depth)
+        make_clip(clip, w, h, a.frames, seed=4321, csp=a.csp, depth=a.input_depth, fade=a.fade)
     args = ["--input", clip, "--input-res", a.res, "--input-depth", str(a.input_depth), "--fps", "30", "--frames", str(a.frames), "--preset", a.preset, "--hash", "1"]
     args += (["--input-csp", a.csp] if a.csp != "i420" else []) + a.extra.split()
     ref = run(os.path.join(REF, "x265_%dbit" % a.bits), args, "/tmp/ab_ref.hevc", dict(os.environ))

@@ -172,6 +172,13 @@ PROTOTYPES = {
     "x265hip_edge_planes": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, i64, vp, i32, C.POINTER(i32), vp]),
     "x265hip_scene_stats": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
     "x265hip_picture_hash": (i32, [i32, i32, vp, i32, vp, vp]),
+    "x265hip_wpcost_begin": (i32, [i32, i32, vp]),
+    "x265hip_wpcost_set_luma": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+    "x265hip_wpcost_set_chroma": (i32, [vp, i32, vp, vp, i64, i32, i32, vp, i32, i32]),
+    "x265hip_wpcost_blocks": (i32, [vp, i32]),
+    "x265hip_wpcost_eval": (i32, [vp, i32, vp, i32, vp, vp]),
+    "x265hip_wpcost_stats": (None, [vp, vp, vp, vp]),
+    "x265hip_wpcost_end": (None, [vp]),
     "x265hip_refpic_create": (vp, [i32, i32, i32, i64, i32, i32, i32, vp]),
     "x265hip_refpic_destroy": (None, [vp]),
     "x265hip_refpic_reset": (i32, [vp]),
