@@ -529,7 +529,8 @@ int x265hip_lowres_intra_estimate(int depth, const void* plane, int64_t stride, 
  * Lowres::lowresQPelCost, lowres.h:94), + 4 against the block's intra cost, frame score over the non-edge blocks, and the
  * AQ-scaled flavour of the score and of the row sums when `invQscale` is given (:3353-3384).
  * Rows are walked bottom-up in `numSlices` independent slices of `numRowsPerSlice` rows (the reference's cooperative
- * lookahead slices, :3092-3104; 1 slice = the serial loop :3170-3179).  No HME.  A weighted reference (weightp) is the same
+ * lookahead slices, :3092-3104; 1 slice = the serial loop :3170-3179).  No HME here: the two levels of an --hme encode are
+ * x265hip_lookahead_cost_hme_batch below.  A weighted reference (weightp) is the same
  * pass with `ref` pointing at the weighted planes (x265hip_lookahead_weights_analyse).
  * All pairs share the geometry; planes are border-extended lowres planes (x265hip_lowres_init), `ref` = hpel plane 0 of
  * the reference with planes 1..3 `planeElems` elements apart.  `sync` is ncu u64 of scratch per pair, zeroed once when
@@ -582,6 +583,65 @@ typedef struct x265hip_lookahead_bframe
 int x265hip_lookahead_bidir_batch(int depth, const x265hip_lookahead_bframe* frames, int nFrames, int64_t stride, int64_t planeElems,
                                   int widthInCU, int heightInCU, int64_t* est, void* stream);
 
+/* ---- the two search levels of an --hme encode (hierarchical motion estimation: --hme, --hme-search, --hme-range) ----
+ * estimateCUCost(…, hme) of slicetype.cpp:3216-3324 with the lowres flavour of motionEstimate under ref->isHMELowres (motion.cpp:817).
+ *   level 0  the quarter-resolution planes (Lowres::lowerResPlane[0..3]: stride lumaStride / 2, planes planesize / 2 apart, origin at
+ *            padoffset / 2; lowres.cpp:143-161, :304-314) over the m_4x4Width x m_4x4Height grid, always the UNWEIGHTED reference, the
+ *            same reverse-order predictors and bidir skip rule; writes only mvs / mvCosts (lowerResMvs / lowerResMvCosts) and leaves at
+ *            :3323 — intraCost, lowresCosts, rowSatds, invQscale of the pair are not touched and est gets only the status word.
+ *   level 1  x265hip_lookahead_cost_p_batch's pass over the half-resolution planes with this level's method and range and a FIFTH
+ *            predictor after the four neighbours (:3281-3284): lowerMvs[k] * 2 when lowerMvCosts[k] > 0, measured by SATD in that
+ *            order with strict <, where k = cuX / 2 + (cuY / 2) * widthInCU / 2 — the reference's own expression, evaluated left to
+ *            right: ((cuY / 2) * widthInCU) / 2.  For an odd widthInCU that is not a row pitch at all; it is reproduced as written.
+ * A level is ONE launch on `stream`; run level 0, then level 1 on the same stream with lowerMvs / lowerMvCosts pointing at level 0's
+ * outputs.  No wave waits across levels; within a level the row handshake of x265hip_lookahead_cost_p_batch applies (its own `sync`
+ * scratch of widthInCU * heightInCU words per pair and level, same epoch rule).
+ * method: X265HIP_ME_DIA / HEX / UMH / STAR.  Refused with X265HIP_EINVAL: FULL (its HME-only window rule, motion.cpp:1402-1408) and SEA
+ * (integral planes the lowres has not); range < 1 or > X265HIP_LA_HME_MAX_RANGE; grids above 512 blocks a side (`mvcost` must be the
+ * centre of a row spanning +-65536 quarter-pels, as x265's own is); and every geometry for which the entry cannot show that each
+ * measured block lies inside its plane's allocation [origin - padOffset, origin - padOffset + planeElems) — the inequality is stated
+ * where it is checked (lookahead_hme.hip).  `lower` is level 0's geometry; at level 1 the fifth predictor is taken only when it is given (NULL: four predictors, lowerMvs ignored). */
+#define X265HIP_ME_DIA  0            /* X265_DIA_SEARCH .. X265_STAR_SEARCH (x265.h) */
+#define X265HIP_ME_HEX  1
+#define X265HIP_ME_UMH  2
+#define X265HIP_ME_STAR 3
+#define X265HIP_LA_HME_MAX_RANGE 64
+typedef struct x265hip_lookahead_hme_level
+{
+    int64_t stride;              /* elements between lines of this level's planes */
+    int64_t planeElems;          /* elements between its four hpel planes = one plane's allocation */
+    int64_t padOffset;           /* elements from the start of a plane's allocation to its origin */
+    int32_t widthInCU, heightInCU;
+    int32_t method, range;       /* hmeSearchMethod[level], hmeRange[level] */
+    int32_t numRowsPerSlice, numSlices;
+} x265hip_lookahead_hme_level;
+typedef struct x265hip_lookahead_hme_pair
+{
+    const void*    fenc;         /* this level's plane 0 origin of the frame being costed */
+    const void*    ref;          /* this level's hpel plane 0 origin of the reference (level 1, list 0: may be the weighted planes) */
+    const int32_t* intraCost;    /* as in x265hip_lookahead_pair; level 1 only */
+    int32_t*       mvs;          /* out [ncu][2] */
+    int32_t*       mvCosts;      /* out [ncu] */
+    uint16_t*      lowresCosts;  /* out [ncu]; level 1, bidirList == 0 only */
+    int32_t*       rowSatds;     /* out [heightInCU]; level 1, bidirList == 0 only */
+    uint64_t*      sync;         /* scratch [ncu] of THIS level */
+    const int32_t* invQscale;
+    const int32_t* lowerMvs;     /* level 1: [lowerCount][2] level-0 vectors of the same (frame, list, distance), or NULL: four predictors */
+    const int32_t* lowerMvCosts; /* level 1: [lowerCount] */
+    int32_t        lowerCount;   /* entries of the two arrays (m_4x4Width * m_4x4Height) */
+    int32_t        bidirList;    /* as in x265hip_lookahead_pair */
+    int32_t        sliceGeom;    /* as in x265hip_lookahead_pair, for this level's rows */
+    int32_t        reserved;
+} x265hip_lookahead_hme_pair;
+int x265hip_lookahead_cost_hme_batch(int depth, const x265hip_lookahead_hme_pair* pairs, int nPairs, int level,
+                                     const x265hip_lookahead_hme_level* geom, const x265hip_lookahead_hme_level* lower,
+                                     const uint16_t* mvcost, uint32_t epoch, int64_t* est, void* stream);
+/* The ownership rule of cooperative slices under HME (slicetype.cpp:3081-3107): a slice runs its level-0 rows, then its level-1 rows,
+ * and slices run concurrently, so an estimate is reproducible only when every level-0 entry a slice's level-1 rows read (index k
+ * above) was written by that slice's own level-0 rows.  Returns 1 when that holds for the geometry (and every k is inside the level-0
+ * grid), 0 otherwise.  numSlices == 1 always holds when the indices are inside.  Pure host arithmetic; no device needed. */
+int x265hip_lookahead_hme_slices_ok(int widthInCU8, int heightInCU8, int widthInCU4, int heightInCU4, int numRowsPerSlice8, int numSlices);
+
 /* ---------------------------------------------------------------- the lookahead session (x265's batching seam) ---- */
 /* What an x265 build binds where the reference itself batches lookahead work: CostEstimateGroup::add / finishBatch
  * (slicetype.cpp:3027-3048, up to 512 estimates per batch) and estimateFrameCost (:3115-3214).  The session mirrors x265's Lowres
@@ -614,6 +674,29 @@ void x265hip_la_destroy(x265hip_la* la);
  * planes, contiguous (Lowres::buffer[0], 4 * planeElems pixels); intraCost [ncu]; invQscale [ncu] (invQscaleFactor, or
  * invQscaleFactor8x8 for qg-size 8) or NULL when the encoder allocates none.  Forgets every vector stored for the slot. */
 int x265hip_la_set_frame(x265hip_la* la, int slot, const void* buffers, const int32_t* intraCost, const int32_t* invQscale);
+/* ---- sessions of --hme encodes (the x265hip_lahme_* entries: not part of the x265hip_la_* set every implementation of the session ABI has).
+ * x265hip_lahme_features() tells a binding what this library's sessions serve (a binding linked against an older library
+ * declares the symbols below weak and finds them absent).  An HME session runs every search of x265hip_la_estimate_batch* as two launches —
+ * x265hip_lookahead_cost_hme_batch at level 0 over the slots' quarter-resolution planes, then at level 1 — with everything else (slots, the vector store,
+ * weighted ids for list 0 of level 1 only, searches ahead, per-pair slice geometry) keyed exactly as before.  Level-0 vectors and costs never leave the
+ * session: the reference reads lowerResMvs only for a list it searches in the same estimate (slicetype.cpp:3258-3262 leaves before :3281).
+ * create_hme: place < 0 = the current device (x265hip_la_create), otherwise x265hip_la_create_at's place.  NULL when a method, a range or a level's
+ * geometry is refused (x265hip_lookahead_cost_hme_batch's rules; x265hip_last_error() says which).  A batch whose slice geometry fails
+ * x265hip_lookahead_hme_slices_ok, or that reads a slot whose quarter-resolution planes were not set after its last x265hip_la_set_frame, is X265HIP_EINVAL. */
+#define X265HIP_LA_FEATURE_HME 1
+int x265hip_lahme_features(void);
+typedef struct x265hip_la_hme_config
+{
+    int32_t method0, method1;        /* hmeSearchMethod[0], [1] (X265HIP_ME_*) */
+    int32_t range0, range1;          /* hmeRange[0], [1] */
+    int64_t lowerStride;             /* lumaStride / 2 */
+    int64_t lowerPlaneElems;         /* planesize / 2: elements between the four lower planes */
+    int64_t lowerPadOffset;          /* padoffset / 2: lowerResPlane[0] - lowerResBuffer[0] */
+    int32_t widthInCU4, heightInCU4; /* m_4x4Width, m_4x4Height */
+} x265hip_la_hme_config;
+x265hip_la* x265hip_lahme_create(int place, const x265hip_la_config* cfg, const x265hip_la_hme_config* hme);
+/* Lowres::lowerResBuffer[0] (4 * lowerPlaneElems pixels) of the frame in `slot`, after its x265hip_la_set_frame */
+int x265hip_lahme_set_frame_lower(x265hip_la* la, int slot, const void* lowerBuffers);
 /* vectors of a search the session has not seen (done by another path): mvs [ncu][2] quarter-pel, mvCosts [ncu] */
 int x265hip_la_put_vectors(x265hip_la* la, int slot, int list, int dist, const int32_t* mvs, const int32_t* mvCosts);
 int x265hip_la_has_vectors(x265hip_la* la, int slot, int list, int dist);

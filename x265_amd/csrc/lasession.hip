@@ -27,6 +27,8 @@ struct LaSlot
     int32_t* invQscale = nullptr;    // [ncu], meaningful when hasInvQ
     int32_t* store = nullptr;        // [2][maxDist][3 * ncu]: mvs (2 ncu) then mvCosts (ncu)
     bool     live = false, hasInvQ = false;
+    char*    lower = nullptr;        // HME sessions: 4 * lowerPlaneElems pixels (Lowres::lowerResBuffer[0..3]), valid when hasLower
+    bool     hasLower = false;
     std::vector<uint8_t> valid;      // [2 * maxDist]
     // searches done ahead of their request (x265hip_la_search): [2][maxDist][4 variants = bidir * 2 + (numSlices > 1)][3 * ncu], allocated on first use
     int32_t* ahead = nullptr;
@@ -57,6 +59,15 @@ struct x265hip_la
     char* dDesc = nullptr; char* hDesc = nullptr; size_t descBytes = 0;     // pairs / pcost pairs / bframes / scatter jobs
     uint64_t statBatches = 0, statEstimates = 0, statSearches = 0;
     uint64_t statAheadLaunched = 0, statAheadUsed = 0, statSearchLaunches = 0, statSearchPairs = 0;
+    // --hme (x265hip_lahme_create): every search is two launches, level 0 over the slots' quarter-resolution planes, then level 1.  Level-0 vectors and
+    // costs are scratch of the batch: the reference reads them only in the estimate that searched them (slicetype.cpp:3258-3262 leaves before :3281).
+    bool hme = false;
+    x265hip_la_hme_config hcfg;
+    int ncu4 = 0;
+    int32_t* dLow = nullptr;         // [2 capEst][3 ncu4]: level-0 mvs (2 ncu4) then costs (ncu4) per search pair
+    uint64_t* dSync0 = nullptr;      // [2 capEst][ncu4]
+    int64_t* dEst0 = nullptr; int64_t* hEst0 = nullptr;                     // [2 capEst][4]: level 0's status words
+    uint64_t statHmePairs = 0;
 };
 
 namespace xh {
@@ -87,10 +98,17 @@ static int la_grow(x265hip_la* la, int n)
     if (la->dSync) (void)device_free(la->dSync);
     if (la->dDesc) (void)device_free(la->dDesc);
     if (la->hDesc) (void)hipHostFree(la->hDesc);
+    if (la->dLow) (void)device_free(la->dLow);
+    if (la->dSync0) (void)device_free(la->dSync0);
+    if (la->dEst0) (void)device_free(la->dEst0);
+    if (la->hEst0) (void)hipHostFree(la->hEst0);
+    la->dLow = nullptr; la->dSync0 = nullptr; la->dEst0 = la->hEst0 = nullptr;
     la->dOut = la->hOut = la->dDesc = la->hDesc = nullptr; la->dSync = nullptr; la->capEst = 0;
     const size_t blk = est_block_bytes(la);
     la->outBytes = blk * cap + (size_t)cap * 3 * 4 * sizeof(int64_t);        // + est words of the three kernels
     la->descBytes = (size_t)cap * (2 * sizeof(x265hip_lookahead_pair) + sizeof(x265hip_lookahead_pair) + sizeof(x265hip_lookahead_bframe) + 4 * sizeof(ScatterJob));
+    if (la->hme)
+        la->descBytes += (size_t)cap * 4 * sizeof(x265hip_lookahead_hme_pair);          // the searches again, per level
     int e;
     if ((e = check_hip(hipMalloc((void**)&la->dOut, la->outBytes), "la out"))) return e;
     if ((e = check_hip(hipHostMalloc((void**)&la->hOut, la->outBytes, hipHostMallocDefault), "la out pinned"))) return e;
@@ -98,6 +116,14 @@ static int la_grow(x265hip_la* la, int n)
     if ((e = check_hip(hipMemsetAsync(la->dSync, 0, (size_t)2 * cap * la->ncu * sizeof(uint64_t), la->st), "la sync zero"))) return e;
     if ((e = check_hip(hipMalloc((void**)&la->dDesc, la->descBytes), "la desc"))) return e;
     if ((e = check_hip(hipHostMalloc((void**)&la->hDesc, la->descBytes, hipHostMallocDefault), "la desc pinned"))) return e;
+    if (la->hme)
+    {
+        if ((e = check_hip(hipMalloc((void**)&la->dLow, (size_t)2 * cap * 3 * la->ncu4 * sizeof(int32_t)), "la level-0 vectors"))) return e;
+        if ((e = check_hip(hipMalloc((void**)&la->dSync0, (size_t)2 * cap * la->ncu4 * sizeof(uint64_t)), "la level-0 sync"))) return e;
+        if ((e = check_hip(hipMemsetAsync(la->dSync0, 0, (size_t)2 * cap * la->ncu4 * sizeof(uint64_t), la->st), "la level-0 sync zero"))) return e;
+        if ((e = check_hip(hipMalloc((void**)&la->dEst0, (size_t)2 * cap * 4 * sizeof(int64_t)), "la level-0 status"))) return e;
+        if ((e = check_hip(hipHostMalloc((void**)&la->hEst0, (size_t)2 * cap * 4 * sizeof(int64_t), hipHostMallocDefault), "la level-0 status pinned"))) return e;
+    }
     la->capEst = cap;
     return X265HIP_OK;
 }
@@ -120,11 +146,57 @@ static inline int ahead_index(const x265hip_la* la, int list, int dist, int bidi
 }
 static inline int32_t* ahead_of(const x265hip_la* la, const LaSlot& s, int idx) { return s.ahead + (size_t)idx * 3 * la->ncu; }
 
+// the two levels of an HME session for a launch of `rows` x `slices` level-1 slice geometry; level-0 rows per slice as processTasks computes them
+// (slicetype.cpp:3083-3084)
+static int hme_rows4(int H4, int slices)
+{
+    if (slices <= 1) return H4;
+    int r = H4 / slices;
+    r = r > 5 ? r : 5;
+    return r < H4 ? r : H4;
+}
+static void hme_levels(const x265hip_la* la, int rows, int slices, x265hip_lookahead_hme_level& lv0, x265hip_lookahead_hme_level& lv1)
+{
+    const x265hip_la_config& c = la->cfg;
+    const x265hip_la_hme_config& h = la->hcfg;
+    lv1 = x265hip_lookahead_hme_level{ c.stride, c.planeElems, c.padOffset, c.widthInCU, c.heightInCU, h.method1, h.range1, rows, slices };
+    lv0 = x265hip_lookahead_hme_level{ h.lowerStride, h.lowerPlaneElems, h.lowerPadOffset, h.widthInCU4, h.heightInCU4, h.method0, h.range0,
+                                       hme_rows4(h.heightInCU4, slices), slices };
+}
+
 } // namespace xh
 
 using namespace xh;
 
 extern "C" {
+
+int x265hip_lahme_features(void) { return X265HIP_LA_FEATURE_HME; }
+
+x265hip_la* x265hip_lahme_create(int place, const x265hip_la_config* cfg, const x265hip_la_hme_config* hme)
+{
+    if (!hme || hme->widthInCU4 < 1 || hme->heightInCU4 < 1 || hme->lowerStride < 8 || hme->lowerPlaneElems < 1 || hme->lowerPadOffset < 0)
+    {
+        set_error(X265HIP_EINVAL, "x265hip_lahme_create: bad HME configuration");
+        return nullptr;
+    }
+    x265hip_la* la = place >= 0 ? x265hip_la_create_at(place, cfg) : x265hip_la_create(cfg);
+    if (!la) return nullptr;
+    la->hme = true;
+    la->hcfg = *hme;
+    la->ncu4 = hme->widthInCU4 * hme->heightInCU4;
+    // methods, ranges and both levels' plane geometry are judged once, by the entry that will launch them (an empty batch validates and returns)
+    x265hip_lookahead_hme_level lv0, lv1;
+    hme_levels(la, cfg->heightInCU, 1, lv0, lv1);
+    int64_t none = 0;
+    (void)hipSetDevice(la->device);
+    if (x265hip_lookahead_cost_hme_batch(cfg->depth, nullptr, 0, 0, &lv0, nullptr, la->mvcost + kMvcostHalf, 1, &none, la->st) ||
+        x265hip_lookahead_cost_hme_batch(cfg->depth, nullptr, 0, 1, &lv1, &lv0, la->mvcost + kMvcostHalf, 1, &none, la->st))
+    {
+        x265hip_la_destroy(la);          // x265hip_last_error() keeps the entry's reason
+        return nullptr;
+    }
+    return la;
+}
 
 x265hip_la* x265hip_la_create(const x265hip_la_config* cfg)
 {
@@ -182,6 +254,7 @@ void x265hip_la_destroy(x265hip_la* la)
         if (s.invQscale) (void)device_free(s.invQscale);
         if (s.store) (void)device_free(s.store);
         if (s.ahead) (void)device_free(s.ahead);
+        if (s.lower) (void)device_free(s.lower);
     }
     for (char* w : la->wbufs) (void)device_free(w);
     if (la->mvcost) (void)device_free(la->mvcost);
@@ -191,6 +264,10 @@ void x265hip_la_destroy(x265hip_la* la)
     if (la->dDesc) (void)device_free(la->dDesc);
     if (la->hDesc) (void)hipHostFree(la->hDesc);
     if (la->hStage) (void)hipHostFree(la->hStage);
+    if (la->dLow) (void)device_free(la->dLow);
+    if (la->dSync0) (void)device_free(la->dSync0);
+    if (la->dEst0) (void)device_free(la->dEst0);
+    if (la->hEst0) (void)hipHostFree(la->hEst0);
     if (la->st) (void)hipStreamDestroy(la->st);
     delete la;
 }
@@ -233,6 +310,31 @@ int x265hip_la_set_frame(x265hip_la* la, int slot, const void* buffers, const in
     std::fill(s.valid.begin(), s.valid.end(), 0);            // Lowres::init resets every search (lowres.cpp:289-295)
     std::fill(s.aheadInfo.begin(), s.aheadInfo.end(), LaSlot::AheadInfo());
     s.live = true;
+    s.hasLower = false;                                       // the frame's quarter-resolution planes follow (x265hip_lahme_set_frame_lower)
+    return X265HIP_OK;
+}
+
+int x265hip_lahme_set_frame_lower(x265hip_la* la, int slot, const void* lowerBuffers)
+{
+    int e = la_enter(la);
+    if (e) return e;
+    if (!la->hme || slot < 0 || slot >= (int)la->slots.size() || !lowerBuffers || !la->slots[slot].live)
+        return set_error(X265HIP_EINVAL, "x265hip_lahme_set_frame_lower: slot %d (an HME session, after x265hip_la_set_frame)", slot);
+    std::lock_guard<std::mutex> g(la->lock);
+    LaSlot& s = la->slots[slot];
+    const size_t bytes = (size_t)4 * la->hcfg.lowerPlaneElems * la->B;
+    if (!s.lower && (e = check_hip(hipMalloc((void**)&s.lower, bytes), "la slot lower planes"))) return e;
+    if (la->hStageBytes < bytes)
+    {
+        if (la->hStage) (void)hipHostFree(la->hStage);
+        la->hStage = nullptr; la->hStageBytes = 0;
+        if ((e = check_hip(hipHostMalloc((void**)&la->hStage, bytes, hipHostMallocDefault), "la staging"))) return e;
+        la->hStageBytes = bytes;
+    }
+    memcpy(la->hStage, lowerBuffers, bytes);
+    if ((e = check_hip(hipMemcpyAsync(s.lower, la->hStage, bytes, hipMemcpyHostToDevice, la->st), "la lower planes h2d"))) return e;
+    if ((e = check_hip(hipStreamSynchronize(la->st), "la set_frame_lower sync"))) return e;
+    s.hasLower = true;
     return X265HIP_OK;
 }
 
@@ -338,6 +440,8 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
     int64_t* dEstSearch = (int64_t*)(la->dOut + blk * la->capEst);
     int nPairs = 0, nPcost = 0, nBf = 0, nSc = 0;
     std::vector<int> pairOfEst(n, -1), pcostOfEst(n, -1), bfOfEst(n, -1);
+    struct PairSlots { int b, ref; };
+    std::vector<PairSlots> pairSlots;                        // HME: whose quarter-resolution planes level 0 of search pair i reads
     // vectors this call produces: they become visible to later calls (valid[] / aheadInfo[]) only after the final synchronise succeeded, and
     // a later estimate of THIS call that reuses them reads the producer's block directly (the slot store is filled by the scatter at the end)
     struct Produced { int slot, list, dist; const int32_t* where; };
@@ -345,6 +449,15 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
     struct AheadDone { int slot, idx, rows, slices; };
     std::vector<AheadDone> aheadDone;
     auto slice_geom = [&](int rows, int slices) { return (rows == numRowsPerSlice && slices == numSlices) ? 0 : (rows | slices << 16); };
+    // HME: what a search needs beyond the one-level pass, judged before anything of the call is built or counted
+    auto hme_search_ok = [&](int slotB, int slotRef, int rows, int slices) {
+        if (!la->hme) return X265HIP_OK;
+        if (!la->slots[slotB].hasLower || !la->slots[slotRef].hasLower)
+            return set_error(X265HIP_EINVAL, "x265hip_la_estimate_batch: a search reads slot %d or %d without quarter-resolution planes (x265hip_lahme_set_frame_lower)", slotB, slotRef);
+        if (!x265hip_lookahead_hme_slices_ok(c.widthInCU, c.heightInCU, la->hcfg.widthInCU4, la->hcfg.heightInCU4, rows, slices))
+            return set_error(X265HIP_EINVAL, "x265hip_la_estimate_batch: %d slices of %d rows: a slice's level-1 rows would read level-0 rows of another slice", slices, rows);
+        return X265HIP_OK;
+    };
     for (int i = 0; i < n; i++)
     {
         x265hip_la_estimate& q = est[i];
@@ -391,6 +504,7 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
                 la->statAheadUsed++;
                 continue;
             }
+            if ((e = hme_search_ok(q.b, l ? q.p1 : q.p0, numRowsPerSlice, numSlices))) return e;
             const LaSlot& fr = la->slots[l ? q.p1 : q.p0];
             const char* refBuf = (!l && q.weightedId >= 0) ? la->wbufs[q.weightedId] : fr.buffers;
             x265hip_lookahead_pair& p = hPairs[nPairs];
@@ -406,6 +520,7 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
             p.invQscale = invQ;
             p.bidirList = bidir ? 1 : 0;
             if (!bidir) { pairOfEst[i] = nPairs; searchedHere0 = true; }
+            pairSlots.push_back(PairSlots{ q.b, l ? q.p1 : q.p0 });
             nPairs++;
             useMvs[l] = oMvs[l];
             hSc[nSc].src = oMvs[l];
@@ -454,6 +569,7 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
         bool dup = false;
         for (const AheadDone& d : aheadDone) dup = dup || (d.slot == a.b && d.idx == idx);
         if (dup) continue;
+        if ((e = hme_search_ok(a.b, a.ref, a.numRowsPerSlice, a.numSlices))) return e;
         if (!fb.ahead && (e = check_hip(hipMalloc((void**)&fb.ahead, (size_t)2 * c.maxDist * 4 * 3 * ncu * 4), "la slot searches ahead"))) return e;
         char* scratchBlk = la->dOut + blk * (n + j);
         int32_t* oRows = (int32_t*)scratchBlk + 6 * ncu;
@@ -471,21 +587,71 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
         p.invQscale = fb.hasInvQ ? fb.invQscale : nullptr;
         p.bidirList = a.bidir ? 1 : 0;
         p.sliceGeom = slice_geom(a.numRowsPerSlice, a.numSlices);
+        pairSlots.push_back(PairSlots{ a.b, a.ref });
         nPairs++;
         aheadDone.push_back(AheadDone{ a.b, idx, a.numRowsPerSlice, a.numSlices });
         la->statAheadLaunched++;
     }
     int64_t* dEstPcost = dEstSearch + (size_t)nPairs * 4;
     int64_t* dEstBf = dEstPcost + (size_t)nPcost * 4;
+    // HME: every search pair again as a level-0 pair over the slots' quarter-resolution planes (always the unweighted reference, slicetype.cpp:3222) and as
+    // a level-1 pair that reads level 0's vectors; the variants (bidir flavour, weighted id, slice geometry) stay keyed exactly as without HME
+    x265hip_lookahead_hme_pair* hP0 = (x265hip_lookahead_hme_pair*)(hSc + 4 * la->capEst);
+    x265hip_lookahead_hme_pair* hP1 = hP0 + 2 * la->capEst;
+    x265hip_lookahead_hme_level lv0, lv1;
+    if (la->hme && nPairs)
+    {
+        hme_levels(la, numRowsPerSlice, numSlices, lv0, lv1);
+        const int W4 = la->hcfg.widthInCU4, H4 = la->hcfg.heightInCU4;
+        for (int i = 0; i < nPairs; i++)
+        {
+            const x265hip_lookahead_pair& p = hPairs[i];
+            const LaSlot& fb = la->slots[pairSlots[i].b];
+            const LaSlot& fr = la->slots[pairSlots[i].ref];
+            const int rows = p.sliceGeom ? (p.sliceGeom & 0xffff) : numRowsPerSlice, slices = p.sliceGeom ? (p.sliceGeom >> 16) : numSlices;
+            int32_t* low = la->dLow + (size_t)i * 3 * la->ncu4;
+            x265hip_lookahead_hme_pair& a = hP0[i];
+            memset(&a, 0, sizeof(a));
+            a.fenc = fb.lower + la->hcfg.lowerPadOffset * B;
+            a.ref = fr.lower + la->hcfg.lowerPadOffset * B;
+            a.mvs = low;
+            a.mvCosts = low + 2 * la->ncu4;
+            a.sync = la->dSync0 + (size_t)i * la->ncu4;
+            a.bidirList = p.bidirList;
+            a.sliceGeom = p.sliceGeom ? (hme_rows4(H4, slices) | slices << 16) : 0;
+            x265hip_lookahead_hme_pair& z = hP1[i];
+            memset(&z, 0, sizeof(z));
+            z.fenc = p.fenc; z.ref = p.ref; z.intraCost = p.intraCost; z.mvs = p.mvs; z.mvCosts = p.mvCosts; z.lowresCosts = p.lowresCosts;
+            z.rowSatds = p.rowSatds; z.sync = p.sync; z.invQscale = p.invQscale; z.bidirList = p.bidirList; z.sliceGeom = p.sliceGeom;
+            z.lowerMvs = low;
+            z.lowerMvCosts = low + 2 * la->ncu4;
+            z.lowerCount = la->ncu4;
+        }
+    }
     if ((e = check_hip(hipMemcpyAsync(la->dDesc, la->hDesc, la->descBytes, hipMemcpyHostToDevice, la->st), "la desc h2d"))) return e;
     if (++la->epoch == 0)
     {
         // 2^32 launches later: start over on a clean scratch
         if ((e = check_hip(hipMemsetAsync(la->dSync, 0, (size_t)2 * la->capEst * ncu * sizeof(uint64_t), la->st), "la sync zero"))) return e;
+        if (la->hme && (e = check_hip(hipMemsetAsync(la->dSync0, 0, (size_t)2 * la->capEst * la->ncu4 * sizeof(uint64_t), la->st), "la level-0 sync zero"))) return e;
         la->epoch = 1;
     }
     DevSpan spanSearch(X265HIP_CLK_LA_SEARCH, la->st);
-    if (nPairs)
+    if (nPairs && la->hme)
+    {
+        // two launches on the session's stream, level 0 first: no wave ever waits for another level
+        if ((e = x265hip_lookahead_cost_hme_batch(c.depth, (const x265hip_lookahead_hme_pair*)dev_of(hP0), nPairs, 0, &lv0, nullptr, la->mvcost + kMvcostHalf, la->epoch,
+                                                  la->dEst0, la->st)))
+            return e;
+        if ((e = x265hip_lookahead_cost_hme_batch(c.depth, (const x265hip_lookahead_hme_pair*)dev_of(hP1), nPairs, 1, &lv1, &lv0, la->mvcost + kMvcostHalf, la->epoch,
+                                                  dEstSearch, la->st)))
+            return e;
+        if ((e = check_hip(hipMemcpyAsync(la->hEst0, la->dEst0, (size_t)nPairs * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, la->st), "la level-0 status d2h"))) return e;
+        la->statSearchLaunches += 2;
+        la->statSearchPairs += 2 * nPairs;
+        la->statHmePairs += nPairs;
+    }
+    else if (nPairs)
     {
         if ((e = x265hip_lookahead_cost_p_batch(c.depth, (const x265hip_lookahead_pair*)dev_of(hPairs), nPairs, c.stride, c.planeElems, W, H, numRowsPerSlice,
                                                 numSlices, la->mvcost + kMvcostHalf, la->epoch, dEstSearch, la->st)))
@@ -515,7 +681,7 @@ int x265hip_la_estimate_batch_ahead(x265hip_la* la, x265hip_la_estimate* est, in
     const int64_t* hEstPcost = hEst + (size_t)nPairs * 4;
     const int64_t* hEstBf = hEstPcost + (size_t)nPcost * 4;
     for (int i = 0; i < nPairs; i++)
-        if (hEst[4 * i + 3])
+        if (hEst[4 * i + 3] || (la->hme && la->hEst0[4 * i + 3]))
             return set_error(X265HIP_EHIP, "x265hip_la_estimate_batch: row handshake of search %d timed out", i);
     // everything arrived: the produced vectors are now the session's
     for (const Produced& pr : produced)

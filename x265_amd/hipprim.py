@@ -153,6 +153,8 @@ PROTOTYPES = {
                                                    vp, i32, i32, vp, vp, vp]),
     "x265hip_lookahead_cost_p_batch": (i32, [i32, vp, i32, i64, i64, i32, i32, i32, i32, vp, u32, vp, vp]),
     "x265hip_lookahead_bidir_batch": (i32, [i32, vp, i32, i64, i64, i32, i32, vp, vp]),
+    "x265hip_lookahead_cost_hme_batch": (i32, [i32, vp, i32, i32, vp, vp, vp, u32, vp, vp]),
+    "x265hip_lookahead_hme_slices_ok": (i32, [i32, i32, i32, i32, i32, i32]),
     "x265hip_lookahead_pcost_batch": (i32, [vp, i32, i32, i32, vp, vp]),
     "x265hip_build_integral_planes": (i32, [i32, vp, i64, i32, vp, i64, vp, vp]),
     "x265hip_motion_estimate_sea_batch": (i32, [i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
@@ -160,6 +162,9 @@ PROTOTYPES = {
     "x265hip_la_create_at": (vp, [i32, vp]),
     "x265hip_la_destroy": (None, [vp]),
     "x265hip_la_set_frame": (i32, [vp, i32, vp, vp, vp]),
+    "x265hip_lahme_features": (i32, []),
+    "x265hip_lahme_create": (vp, [i32, vp, vp]),
+    "x265hip_lahme_set_frame_lower": (i32, [vp, i32, vp]),
     "x265hip_la_put_vectors": (i32, [vp, i32, i32, i32, vp, vp]),
     "x265hip_la_has_vectors": (i32, [vp, i32, i32, i32]),
     "x265hip_la_weights_analyse": (i32, [vp, i32, i32, u64, u64, u64, u64, vp, vp, vp]),
@@ -252,10 +257,29 @@ class LookaheadPair(C.Structure):
                 ("invQscale", vp), ("bidirList", C.c_int32), ("sliceGeom", C.c_int32)]
 
 
+class LookaheadHmeLevel(C.Structure):
+    """x265hip_lookahead_hme_level (include/x265hip.h)"""
+    _fields_ = [("stride", C.c_int64), ("planeElems", C.c_int64), ("padOffset", C.c_int64), ("widthInCU", C.c_int32), ("heightInCU", C.c_int32),
+                ("method", C.c_int32), ("range", C.c_int32), ("numRowsPerSlice", C.c_int32), ("numSlices", C.c_int32)]
+
+
+class LookaheadHmePair(C.Structure):
+    """x265hip_lookahead_hme_pair (include/x265hip.h)"""
+    _fields_ = [("fenc", vp), ("ref", vp), ("intraCost", vp), ("mvs", vp), ("mvCosts", vp), ("lowresCosts", vp), ("rowSatds", vp), ("sync", vp),
+                ("invQscale", vp), ("lowerMvs", vp), ("lowerMvCosts", vp), ("lowerCount", C.c_int32), ("bidirList", C.c_int32), ("sliceGeom", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class LaConfig(C.Structure):
     """x265hip_la_config (include/x265hip.h)"""
     _fields_ = [("depth", C.c_int32), ("width", C.c_int32), ("lines", C.c_int32), ("stride", C.c_int64), ("planeElems", C.c_int64), ("padOffset", C.c_int64),
                 ("widthInCU", C.c_int32), ("heightInCU", C.c_int32), ("maxDist", C.c_int32), ("numSlots", C.c_int32)]
+
+
+class LaHmeConfig(C.Structure):
+    """x265hip_la_hme_config (include/x265hip.h)"""
+    _fields_ = [("method0", C.c_int32), ("method1", C.c_int32), ("range0", C.c_int32), ("range1", C.c_int32), ("lowerStride", C.c_int64),
+                ("lowerPlaneElems", C.c_int64), ("lowerPadOffset", C.c_int64), ("widthInCU4", C.c_int32), ("heightInCU4", C.c_int32)]
 
 
 class LaEstimate(C.Structure):

@@ -16,11 +16,13 @@
 // file restates none of the reference's control flow: when the cache test says "not computed yet" it computes on the GPU and fills the
 // Lowres arrays, then ALWAYS finishes through the reference's own estimateFrameCost, which finds its cache filled (:3121-3122).
 //
-// Without a usable device, or with X265HIP_LOOKAHEAD=0, or for configurations the device pass does not cover (HME, aq-motion), every call
+// Without a usable device, or with X265HIP_LOOKAHEAD=0, or for configurations the device pass does not cover (aq-motion; HME with
+// X265HIP_LOOKAHEAD_HME=0, in the Main12 build unless it is 1, or against a library without the HME session), every call
 // goes to the reference's original code.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <pthread.h>
@@ -38,6 +40,15 @@
 
 #include "x265hip.h"
 #include "x265_hip_debug.h"
+
+// The HME entries are newer than the rest of the session ABI: weak, so that a binding linked against a library without them (the CPU emulation of
+// tests/support, an older libx265hip) loads and keeps --hme encodes on the host.
+extern "C" {
+int x265hip_lahme_features(void) __attribute__((weak));
+x265hip_la* x265hip_lahme_create(int place, const x265hip_la_config* cfg, const x265hip_la_hme_config* hme) __attribute__((weak));
+int x265hip_lahme_set_frame_lower(x265hip_la* la, int slot, const void* lowerBuffers) __attribute__((weak));
+int x265hip_lookahead_hme_slices_ok(int widthInCU8, int heightInCU8, int widthInCU4, int heightInCU4, int numRowsPerSlice8, int numSlices) __attribute__((weak));
+}
 
 namespace X265_NS {
 
@@ -76,6 +87,11 @@ uint64_t g_useClock = 0;
 int g_state = 0;                 // 0 = not decided, 1 = on, -1 = off
 bool g_verbose = false, g_trace = false;
 bool g_ahead = true;             // X265HIP_LOOKAHEAD_AHEAD=0: no searches ahead of the reference's requests (for A/B measurements)
+bool g_hme = false;              // X265HIP_LOOKAHEAD_HME=1 / =0: --hme encodes are served too (two search levels per estimate); the default is set in enabled()
+std::atomic<uint64_t> g_hmeBatched(0), g_hmeSingle(0), g_hmeRefusedSlices(0);     // HME estimates searched in batches / one at a time / left to the host
+std::atomic<bool> g_hmeDeclined(false);                  // the library refused the HME session's geometry: such encodes stay on the host, quietly
+bool g_hmeSeen = false;                                  // an HME session existed (under g_lock); its methods and ranges, for the report:
+int g_hmeShape[4] = { 0, 0, 0, 0 };
 
 // totals of the sessions that were closed with their encoders (Lookahead::destroy below)
 uint64_t g_pastBatches = 0, g_pastEstimates = 0, g_pastSearches = 0, g_pastUploads = 0, g_pastWaitNs = 0;
@@ -114,11 +130,15 @@ void report()
             for (int i = 0; i < 4; i++) ahead[i] += ah[i];
             any = true;
         }
-    if (!any)
+    if (!any && !g_hmeRefusedSlices.load())
         return;
     fprintf(stderr, "x265hip: lookahead: %llu frame-cost estimates (%llu motion-search passes over %llu lowres frames) served by the GPU in %llu batches, %.3f s inside the seam\n",
             (unsigned long long)estimates, (unsigned long long)searches, (unsigned long long)uploads, (unsigned long long)batches,
             waitNs * 1e-9);
+    if (g_hmeSeen || g_hmeRefusedSlices.load())
+        fprintf(stderr, "x265hip: lookahead: hme: %llu estimates searched with two levels (%llu of them single estimates; methods %d,%d ranges %d,%d), %llu left to the host for their slice geometry\n",
+                (unsigned long long)(g_hmeBatched.load() + g_hmeSingle.load()), (unsigned long long)g_hmeSingle.load(), g_hmeShape[0], g_hmeShape[1], g_hmeShape[2], g_hmeShape[3],
+                (unsigned long long)g_hmeRefusedSlices.load());
     fprintf(stderr, "x265hip: lookahead: %llu searches launched ahead of their request, %llu of them used; %llu search launches of %.1f (frame, reference) pairs on average\n",
             (unsigned long long)ahead[0], (unsigned long long)ahead[1], (unsigned long long)ahead[2], ahead[2] ? (double)ahead[3] / ahead[2] : 0.0);
 }
@@ -133,6 +153,9 @@ bool enabled()
         g_trace = getenv("X265HIP_DEBUG_TRACE") != NULL;
         const char* ahead = getenv("X265HIP_LOOKAHEAD_AHEAD");
         g_ahead = !(ahead && !strcmp(ahead, "0"));
+        const char* hme = getenv("X265HIP_LOOKAHEAD_HME");
+        // on where it was measured ahead by more than the host leg's own spread (profiles/r17_v1_hme_ab.txt: the 8-bit and the 10-bit build); Main12 was not measured
+        g_hme = hme ? !strcmp(hme, "1") : X265_DEPTH < 12;
         if ((env && !strcmp(env, "0")) || (all && !strcmp(all, "0")) || x265hip_device_count() < 1)
             g_state = -1;
         else
@@ -147,12 +170,36 @@ bool enabled()
 
 // a device call of the estimate path failed: thrown up to compute_guarded(), which hands the estimates back to the reference's own functions
 struct DeviceFailure { const char* what; };
+// the library declined to make the HME session (a level's planes do not hold the search reach): not a failure, the estimates go back the same way
+struct Declined {};
 [[noreturn]] void die(const char* what) { throw DeviceFailure{ what }; }
+
+// --hme: served when switched on, when the library linked in has the HME session, and when both levels use methods and ranges it serves
+// (x265hip_lookahead_cost_hme_batch: DIA, HEX, UMH, STAR up to X265HIP_LA_HME_MAX_RANGE; the planes' geometry is judged when the session is created)
+bool hme_served(const x265_param* p, const Lowres* fenc)
+{
+    if (!g_hme || g_hmeDeclined.load() || !x265hip_lahme_features || !x265hip_lahme_create || !x265hip_lahme_set_frame_lower || !x265hip_lookahead_hme_slices_ok ||
+        !(x265hip_lahme_features() & X265HIP_LA_FEATURE_HME) || !fenc->lowerResBuffer[0])
+        return false;
+    for (int lv = 0; lv < 2; lv++)
+        if (p->hmeSearchMethod[lv] < X265HIP_ME_DIA || p->hmeSearchMethod[lv] > X265HIP_ME_STAR || p->hmeRange[lv] < 1 || p->hmeRange[lv] > X265HIP_LA_HME_MAX_RANGE)
+            return false;
+    return true;
+}
 
 bool covered(const Lookahead& l, const Lowres* fenc)
 {
     const x265_param* p = l.m_param;
-    return !p->bEnableHME && !p->bAQMotion && fenc->buffer[0] && (fenc->buffer[1] - fenc->buffer[0]) < (1 << 24) && p->bframes + 2 <= 18;
+    return (!p->bEnableHME || hme_served(p, fenc)) && !p->bAQMotion && fenc->buffer[0] && (fenc->buffer[1] - fenc->buffer[0]) < (1 << 24) && p->bframes + 2 <= 18;
+}
+
+// The cooperative slices of an HME estimate run level 0 and then level 1 each, concurrently (slicetype.cpp:3081-3107): where a slice's level-1 rows read
+// level-0 rows of another slice the reference races with itself, and the estimate stays with the reference's body.
+bool hme_slices_ok(const Lookahead& l, int rows, int slices)
+{
+    if (!l.m_param->bEnableHME)
+        return true;
+    return x265hip_lookahead_hme_slices_ok(l.m_8x8Width, l.m_8x8Height, l.m_4x4Width, l.m_4x4Height, rows, slices) != 0;    // a few thousand integer operations
 }
 
 Session& session_for(const Lookahead& l, const Lowres* f)
@@ -193,18 +240,38 @@ Session& session_for(const Lookahead& l, const Lowres* f)
     // sit on place 0 beside the first mirror, the first source picture and the first job server
     static int nextPlace = -1;                           // under g_lock (compute() holds it while it asks for the session)
     const int places = x265hip_places_configured();
+    int place = -1;                                      // -1: the current device (one place)
     if (places > 1)
     {
         if (nextPlace < 0) nextPlace = places - 1;
-        s.la = x265hip_la_create_at(nextPlace, &c);
-        s.place = nextPlace;
+        place = nextPlace;
         nextPlace = (nextPlace + places - 1) % places;
     }
-    else
+    s.place = place < 0 ? 0 : place;
+    if (l.m_param->bEnableHME)
     {
-        s.la = x265hip_la_create(&c);
-        s.place = 0;
+        x265hip_la_hme_config h;
+        memset(&h, 0, sizeof(h));
+        h.method0 = l.m_param->hmeSearchMethod[0]; h.method1 = l.m_param->hmeSearchMethod[1];
+        h.range0 = l.m_param->hmeRange[0]; h.range1 = l.m_param->hmeRange[1];
+        h.lowerStride = f->lumaStride / 2;
+        h.lowerPlaneElems = f->lowerResBuffer[1] - f->lowerResBuffer[0];
+        h.lowerPadOffset = f->lowerResPlane[0] - f->lowerResBuffer[0];
+        h.widthInCU4 = l.m_4x4Width; h.heightInCU4 = l.m_4x4Height;
+        s.la = x265hip_lahme_create(place, &c, &h);
+        if (!s.la && x265hip_device_count() > 0)
+        {
+            // NULL with a reason (x265hip_last_error()): a geometry the entry refuses.  The encode's lookahead stays on the host, like a refused method.
+            if (g_verbose)
+                fprintf(stderr, "x265hip: lookahead: hme: the session was declined (%s); the lookahead of this encode stays on the host\n", x265hip_last_error());
+            g_hmeDeclined = true;
+            throw Declined{};
+        }
+        g_hmeSeen = s.la != NULL;
+        g_hmeShape[0] = h.method0; g_hmeShape[1] = h.method1; g_hmeShape[2] = h.range0; g_hmeShape[3] = h.range1;
     }
+    else
+        s.la = place >= 0 ? x265hip_la_create_at(place, &c) : x265hip_la_create(&c);
     x265hip_debug_mark("created: lookahead session");
     if (!s.la)
         die("session");
@@ -242,6 +309,8 @@ int slot_of(Session& s, const Lookahead& l, const Lowres* f)
     const int32_t* invq = f->invQscaleFactor ? (l.m_param->rc.qgSize == 8 ? f->invQscaleFactor8x8 : f->invQscaleFactor) : NULL;
     if (x265hip_la_set_frame(s.la, victim, f->buffer[0], f->intraCost, invq))
         die("frame upload");
+    if (l.m_param->bEnableHME && x265hip_lahme_set_frame_lower(s.la, victim, f->lowerResBuffer[0]))
+        die("frame upload (quarter resolution)");
     s.slots[victim] = SlotEntry{ f, f->frameNum, s.stamp };
     s.uploads++;
     return victim;
@@ -270,6 +339,8 @@ void plan_ahead(Session& s, CostEstimateGroup& g, const Job* jobs, int n, const 
     while (hi + 1 <= bound && g.m_frames[hi + 1])
         hi++;
     const int coopSlices = X265_MAX(1, l.m_numCoopSlices), coopRows = coopSlices > 1 ? l.m_numRowsPerSlice : l.m_8x8Height;
+    if (!hme_slices_ok(l, coopRows, coopSlices))
+        return;                                 // the requests these searches run ahead of will stay with the reference
     auto real = [&](int b, int list, int dist) {
         for (int i = 0; i < n; i++)
             if (jobs[i].b == b && (list ? (est[i].search1 && est[i].dist1 == dist) : (est[i].search0 && est[i].dist0 == dist)))
@@ -392,6 +463,10 @@ void compute(CostEstimateGroup& g, const Job* jobs, int n, bool coop)
         plan_ahead(s, g, jobs, n, est, ahead);
     if (x265hip_la_estimate_batch_ahead(s.la, est.data(), n, rows, slices, ahead.data(), (int)ahead.size()))
         die("estimate batch");
+    if (param->bEnableHME)
+        for (int i = 0; i < n; i++)
+            if (est[i].search0 || est[i].search1)                  // the ones that ran the two levels; the others only read stored level-1 costs
+                (g.m_batchMode ? g_hmeBatched : g_hmeSingle)++;
     for (int i = 0; i < n; i++)
     {
         const Job& j = jobs[i];
@@ -442,13 +517,7 @@ void compute_guarded(CostEstimateGroup& g, const Job* jobs, int n, bool coop)
         before[i].search0 = fenc->lowresMvs[0][jobs[i].b - jobs[i].p0][0].x == 0x7FFF;
         before[i].search1 = jobs[i].p1 > jobs[i].b && fenc->lowresMvs[1][jobs[i].p1 - jobs[i].b][0].x == 0x7FFF;
     }
-    try
-    {
-        compute(g, jobs, n, coop);
-    }
-    catch (const DeviceFailure& f)
-    {
-        g_state = -1;
+    auto undo = [&]() {
         for (int i = 0; i < n; i++)
         {
             Lowres* fenc = g.m_frames[jobs[i].b];
@@ -458,8 +527,38 @@ void compute_guarded(CostEstimateGroup& g, const Job* jobs, int n, bool coop)
             fenc->costEst[d0][d1] = -1;
             fenc->rowSatds[d0][d1][0] = -1;
         }
+    };
+    try
+    {
+        compute(g, jobs, n, coop);
+    }
+    catch (const Declined&)
+    {
+        undo();
+    }
+    catch (const DeviceFailure& f)
+    {
+        g_state = -1;
+        undo();
         x265hip_device_failure("lookahead", f.what);
     }
+}
+
+// one estimate asked for outside a batch (singleCost -> estimateFrameCost): cooperative slices when the pool allows and there is something to search
+void serve_single(CostEstimateGroup& g, int p0, int p1, int b)
+{
+    const Lookahead& l = g.m_lookahead;
+    const Lowres* fenc = g.m_frames[b];
+    const bool search0 = fenc->lowresMvs[0][b - p0][0].x == 0x7FFF;
+    const bool search1 = p1 > b && fenc->lowresMvs[1][p1 - b][0].x == 0x7FFF;
+    const bool coop = !g.m_batchMode && l.m_numCoopSlices > 1 && (p1 > b || search0 || search1);
+    if (coop && !hme_slices_ok(l, l.m_numRowsPerSlice, l.m_numCoopSlices))
+    {
+        g_hmeRefusedSlices++;
+        return;                                 // the reference's own body, races included
+    }
+    const Job j = { p0, p1, b };
+    compute_guarded(g, &j, 1, coop);
 }
 
 } // namespace
@@ -524,27 +623,14 @@ int64_t CostEstimateGroup::estimateFrameCost(LookaheadTLD& tld, int p0, int p1, 
         const long long a = timeline().now();
         const int wasCached = cached(m_frames[b], p0, p1, b);
         if (!wasCached && enabled() && covered(m_lookahead, m_frames[b]))
-        {
-            Lowres* fenc = m_frames[b];
-            const bool search0 = fenc->lowresMvs[0][b - p0][0].x == 0x7FFF;
-            const bool search1 = p1 > b && fenc->lowresMvs[1][p1 - b][0].x == 0x7FFF;
-            const bool coop = !m_batchMode && m_lookahead.m_numCoopSlices > 1 && (p1 > b || search0 || search1);
-            const Job j = { p0, p1, b };
-            compute_guarded(*this, &j, 1, coop);
-        }
+            serve_single(*this, p0, p1, b);
         const int64_t r = refEstimateFrameCost(this, tld, p0, p1, b, bIntraPenalty);
         timeline().line(a, timeline().now(), m_batchMode ? "estB" : "est", p0, p1, m_frames[b]->frameNum, wasCached, 1);
         return r;
     }
     Lowres* fenc = m_frames[b];
     if (!cached(fenc, p0, p1, b) && enabled() && covered(m_lookahead, fenc))
-    {
-        const bool search0 = fenc->lowresMvs[0][b - p0][0].x == 0x7FFF;
-        const bool search1 = p1 > b && fenc->lowresMvs[1][p1 - b][0].x == 0x7FFF;
-        const bool coop = !m_batchMode && m_lookahead.m_numCoopSlices > 1 && (p1 > b || search0 || search1);
-        const Job j = { p0, p1, b };
-        compute_guarded(*this, &j, 1, coop);
-    }
+        serve_single(*this, p0, p1, b);
     return refEstimateFrameCost(this, tld, p0, p1, b, bIntraPenalty);
 }
 
